@@ -15,6 +15,19 @@ Launch (driver contract):
 
 A "step" is one learner update consuming unroll_length*batch_size env steps.
 Rank 0 prints ONE JSON line with the whole-job aggregate SPS.
+
+A plain run does only what that line needs: set up, warm up, time K steps,
+print. `--full` is where any secondary measurement belongs; today there is
+none, so it runs the same thing.
+
+`--dump-outputs DIR` writes what the last timed learner step computed as
+DIR/<name>.npy (float32). The live actor pipeline is racy by design (batch
+composition and behaviour actions depend on thread timing), so in this mode
+every learner step consumes one fixed, seeded rollout batch instead of the
+queue's contents and starts from the initial weights and optimizer state:
+same arguments -> same inputs -> outputs comparable across builds to
+float-reduction noise. The pipeline still runs and its queue is still
+drained every step, so the step does the same work as in a plain run.
 """
 
 import argparse
@@ -24,6 +37,7 @@ import sys
 import threading
 import timeit
 
+import numpy as np
 import torch
 
 import torchbeast_amd.polybeast_learner as pbl
@@ -69,12 +83,56 @@ def parse_args():
     p.add_argument("--no_hipgraph", dest="hipgraph", action="store_false")
     p.add_argument("--py_inference", action="store_true",
                    help="Python inference threads instead of the C++ engine.")
+    p.add_argument("--full", action="store_true",
+                   help="Also run the secondary measurements (none today; "
+                        "a plain run only produces the headline line).")
+    p.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR",
+                   default=None,
+                   help="Feed the learner a fixed seeded batch and write the "
+                        "last timed step's outputs to DIR/<name>.npy.")
     return p.parse_args()
+
+
+DUMP_SEED = 20240
+DUMP_MAX_ELEMS = 1 << 20  # per array; larger ones are sampled (seeded)
+
+
+def seeded_batch(template, num_actions, seed):
+    """A rollout batch with the shapes/dtypes/devices of `template` (one real
+    batch off the learner queue) and contents drawn from a seeded CPU
+    generator, so it is identical from run to run and build to build."""
+    g = torch.Generator().manual_seed(seed)
+    out = []
+    for t in template:
+        shape = tuple(t.shape)
+        if t.dtype == torch.uint8:  # frames
+            v = torch.randint(0, 256, shape, generator=g, dtype=torch.uint8)
+        elif t.dtype == torch.bool:  # done
+            v = torch.rand(shape, generator=g) < 0.01
+        elif t.dtype.is_floating_point:  # rewards, logits, baseline, state
+            v = torch.randn(shape, generator=g).to(t.dtype)
+        else:  # actions, episode_step
+            v = torch.randint(0, num_actions, shape, generator=g).to(t.dtype)
+        out.append(v.to(t.device))
+    return tuple(out)
+
+
+def dump_outputs(dirname, outputs):
+    """Write {name: tensor} as float32 .npy files; arrays over
+    DUMP_MAX_ELEMS are reduced to a fixed seeded sample of their elements."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in outputs.items():
+        a = t.detach().to("cpu", torch.float32).contiguous()
+        if a.numel() > DUMP_MAX_ELEMS:
+            g = torch.Generator().manual_seed(DUMP_SEED)
+            idx = torch.randint(0, a.numel(), (DUMP_MAX_ELEMS,), generator=g)
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), a.numpy())
 
 
 def learner_step(flags, batch_tensors, model, optimizer, scheduler, reducer,
                  actor_flat, flat_param, inference_runner=None,
-                 device_ops_only=False):
+                 device_ops_only=False, outputs=None):
     env_outputs = pbl.EnvOutput._make(batch_tensors[:5])
     actor_outputs = pbl.AgentOutput._make(batch_tensors[5:8])
     initial_agent_state = batch_tensors[8:]
@@ -112,6 +170,19 @@ def learner_step(flags, batch_tensors, model, optimizer, scheduler, reducer,
     )
     total_loss = (pg_loss + flags.baseline_cost * baseline_loss
                   + flags.entropy_cost * entropy_loss)
+    if outputs is not None:
+        # --dump-outputs: keep what this step computed (under hipGraph these
+        # are the static tensors every replay rewrites). Detached: holding
+        # a grad_fn would keep this step's autograd graph, and with it the
+        # AccumulateGrad nodes bound to this stream, alive into the capture.
+        outputs.update(
+            total_loss=total_loss.detach(), pg_loss=pg_loss.detach(),
+            baseline_loss=baseline_loss.detach(),
+            entropy_loss=entropy_loss.detach(),
+            policy_logits=learner_outputs.policy_logits.detach(),
+            baseline=learner_outputs.baseline.detach(),
+            vs=vtr.vs.detach(), pg_advantages=vtr.pg_advantages.detach(),
+        )
 
     optimizer.zero_grad()
     total_loss.backward()
@@ -254,6 +325,28 @@ def main():
 
     queue_iter = iter(learner_queue)
 
+    step_outputs = None
+    if args.dump_outputs:
+        # Deterministic learner inputs: every step still drains one batch
+        # off the live queue, then trains on the fixed seeded one, starting
+        # from the initial weights and optimizer state (two small device
+        # copies per step). Without the reset, float-add reordering in the
+        # reductions (~1e-8 per update) is amplified through bf16 weight
+        # rounding to O(1) differences within a few dozen updates.
+        step_outputs = {}
+        fixed_batch = seeded_batch(get_batch(queue_iter), args.num_actions,
+                                   DUMP_SEED + rank)
+        init_param = flat_param.clone()
+        init_square_avg = optimizer.square_avg.clone()
+        real_get_batch = get_batch
+
+        def get_batch(it):  # noqa: F811
+            real_get_batch(it)
+            with torch.no_grad():
+                flat_param.copy_(init_param)
+                optimizer.square_avg.copy_(init_square_avg)
+            return fixed_batch
+
     graph = None
     static_batch = None
     # Default hipGraph for the non-LSTM configs (the LSTM's cooperative
@@ -267,7 +360,8 @@ def main():
     # Warmup (fills the pipeline, compiles/caches kernels).
     for _ in range(args.warmup):
         learner_step(flags, get_batch(queue_iter), model, optimizer, scheduler,
-                     reducer, actor_flat, flat_param, inference_runner)
+                     reducer, actor_flat, flat_param, inference_runner,
+                     outputs=step_outputs)
 
     if use_graph:
       try:
@@ -291,7 +385,7 @@ def main():
         with torch.cuda.graph(graph, capture_error_mode="thread_local"):
             learner_step(flags, static_batch, model, optimizer, scheduler,
                          reducer, actor_flat, flat_param, None,
-                         device_ops_only=True)
+                         device_ops_only=True, outputs=step_outputs)
       except Exception as e:  # pragma: no cover - device-dependent
         print(f"hipGraph capture failed ({e!r}); falling back to eager",
               file=sys.stderr)
@@ -302,7 +396,7 @@ def main():
         if graph is None:
             learner_step(flags, get_batch(queue_iter), model, optimizer,
                          scheduler, reducer, actor_flat, flat_param,
-                         inference_runner)
+                         inference_runner, outputs=step_outputs)
             return
         batch = get_batch(queue_iter)
         for dst, src in zip(static_batch, batch):
@@ -343,7 +437,8 @@ def main():
             torch.cuda.synchronize()
             timings.time("get_batch")
             learner_step(flags, batch, model, optimizer, scheduler, reducer,
-                         actor_flat, flat_param, inference_runner)
+                         actor_flat, flat_param, inference_runner,
+                         outputs=step_outputs)
             torch.cuda.synchronize()
             timings.time("learn")
 
@@ -366,9 +461,15 @@ def main():
         print(f"learner_queue stats: {learner_queue.stats()}", file=sys.stderr)
         print(f"batcher stats: {inference_batcher.stats()}", file=sys.stderr)
 
+    if step_outputs is not None and rank == 0:
+        step_outputs["grad_norm"] = optimizer.last_grad_norm
+        step_outputs["flat_param"] = flat_param  # weights after the update
+        dump_outputs(args.dump_outputs, step_outputs)
+
     inference_batcher.close()
     learner_queue.close()
-    if inference_runner is not None and os.environ.get("TBAMD_CLEAN_EXIT"):
+    fast_exit = bool(os.environ.get("TBAMD_FAST_EXIT"))
+    if inference_runner is not None and not fast_exit:
         inference_runner.stop()
 
     if rank == 0:
@@ -401,12 +502,13 @@ def main():
 
     if world_size > 1:
         torch.distributed.destroy_process_group()
-    if os.environ.get("TBAMD_CLEAN_EXIT"):
-        # Orderly exit (lets rocprofv3 flush its results); threads are
-        # daemonic and unwind via the closed queues.
-        pool_thread.join(timeout=5)
-        sys.exit(0)
-    os._exit(0)  # Actor/inference threads are daemonic; skip teardown races.
+    if fast_exit:
+        os._exit(0)  # skip teardown entirely (no exit handlers run)
+    # Orderly exit, so exit handlers run and tools that observe the process
+    # (profilers, tracers) can flush what they recorded; threads are daemonic
+    # and unwind via the closed queues.
+    pool_thread.join(timeout=5)
+    sys.exit(0)
 
 
 if __name__ == "__main__":
