@@ -6,12 +6,25 @@
 // src/cc/actorpool.cc:342-564): rollouts overlap by one step (the last step
 // of rollout k is the first of rollout k+1), and the agent state recorded
 // with a rollout is the state *before* the inference of its first step.
+//
+// Two implementations:
+// - loop_rows (default whenever the pool has a rollout budget and is not in
+//   obs-slab mode): every env stream holds a pinned slab slot carved into
+//   [T+1, 1, ...] columns and fills it row by row in place. Envs write their
+//   step into the row (EnvConnection::step_into), requests are row PODs
+//   submitted under one lock per sweep, and the thread blocks on its own
+//   ActorMailbox (queues.h) -- no per-step tensors, promises or polling. A
+//   finished rollout is enqueued as the carved views.
+// - loop / loop_multi (no rollout budget, obs-slab mode, or
+//   TBAMD_ACTOR_FASTPATH=0 for A/B runs): per-step nests, promise/future
+//   requests, rollouts cat-ed at flush time.
 
 #pragma once
 
 #include <algorithm>
 #include <atomic>
 #include <condition_variable>
+#include <cstdlib>
 #include <cstring>
 #include <future>
 #include <mutex>
@@ -46,16 +59,40 @@ class ActorPool {
     if (rollout_budget_mb > 0) {
       // Budget-sized pinned rollout ring with backpressure (replaces
       // unbounded ad-hoc pinned allocations); the learner queue recycles
-      // slots after its H2D assembly completes. Floor at one slot per
-      // actor + slack: an actor blocked on a full learner queue holds its
-      // slot, so fewer slots than actors would throttle the whole pool
-      // below the queue's own backpressure (measured: 7k wait wakeups per
-      // bench run at 326 slots / 512 actors).
+      // slots after its H2D assembly completes.
+      //
+      // Slot floor = actors + learner-queue capacity + two learner batches.
+      // Every slot is FREE, held by a stream, in the learner queue (at most
+      // its capacity Q) or PENDING (read by H2D copies; freed in finite
+      // time whatever the actors do). A stream fills one slot; at the end
+      // of a rollout it acquires the next slot BEFORE it enqueues the
+      // finished one (row T is copied to the new row 0 while the old slot
+      // is still its own), so a stream blocked in acquire() holds exactly
+      // one slot. If every stream were blocked there, streams would hold
+      // `actors` slots and the queue at most Q, so at least two batches'
+      // worth of slots are FREE or PENDING and some acquire() returns:
+      // no deadlock. A stream not in acquire() waits for inference, which
+      // needs no slot, or sits in enqueue() on a full learner queue. The
+      // latter holds TWO slots (the finished one, not yet queued, and its
+      // new one), so streams can hold up to 2 x actors slots in all; but a
+      // full queue means the learner can dequeue -- assuming, as every
+      // driver configures, a queue capacity of at least the learner batch
+      // size -- and each dequeue frees slots and queue room, so those
+      // streams move on without acquiring anything. The two batches are
+      // throughput slack: one batch being copied (PENDING) while the next
+      // one forms.
+      const int64_t queue_cap = learner_queue_->max_queue_size().value_or(64);
+      const int64_t batch =
+          std::min<int64_t>(learner_queue_->max_batch_size(), 1024);
       rollout_pool_ = std::make_shared<PinnedSlabPool>(
           rollout_budget_mb * (1 << 20),
-          /*min_slots=*/(int64_t)addresses_.size() + 64);
+          /*min_slots=*/(int64_t)addresses_.size() + queue_cap + 2 * batch);
       learner_queue_->set_source_pool(rollout_pool_);
     }
+    // TBAMD_ACTOR_FASTPATH=0 keeps the nest/promise loops below (A/B only).
+    const char* fp = std::getenv("TBAMD_ACTOR_FASTPATH");
+    use_rows_ = rollout_pool_ != nullptr && !use_obs_slab_ &&
+                !(fp != nullptr && std::string(fp) == "0");
   }
 
   // Pinned observation slab (slot per actor). Valid once the first env has
@@ -78,7 +115,7 @@ class ActorPool {
   void run() {
     std::vector<std::future<void>> futures;
     const size_t k = (size_t)envs_per_thread_;
-    if (k > 1) {
+    if (k > 1 || use_rows_) {
       // Event-driven mode: each thread drives k env streams with
       // overlapped inference requests. 512 actor threads were measured
       // host-scheduling-bound (serve latency scaled with thread count,
@@ -93,7 +130,11 @@ class ActorPool {
         const size_t hi = std::min(addresses_.size(), lo + k);
         futures.push_back(std::async(std::launch::async, [this, lo, hi] {
           try {
-            loop_multi(lo, hi);
+            if (use_rows_) {
+              loop_rows(lo, hi);
+            } else {
+              loop_multi(lo, hi);
+            }
           } catch (...) {
             {
               std::lock_guard<std::mutex> lk(slab_mu_);
@@ -224,7 +265,12 @@ class ActorPool {
 
     for (size_t i = 0; i < n; ++i) issue(i);
 
+    // CPU-time counters, sampled per sweep: this loop interleaves collect,
+    // env step and issue per env, so all three land under "collect".
+    CpuStageCounters& cnt = learner_queue_->actor_counters();
+    int64_t flush_ns = 0;
     for (;;) {
+      const int64_t c0 = thread_cpu_ns();
       // Block briefly on the first pending future, then sweep all.
       size_t first = n;
       for (size_t i = 0; i < n; ++i) {
@@ -235,6 +281,9 @@ class ActorPool {
       }
       if (first == n) throw std::logic_error("no pending inference");
       envs[first].pending.wait_for(std::chrono::microseconds(500));
+      const int64_t c1 = thread_cpu_ns();
+      int64_t stepped = 0;
+      flush_ns = 0;
 
       for (size_t i = 0; i < n; ++i) {
         EnvSlot& e = envs[i];
@@ -257,18 +306,228 @@ class ActorPool {
             TensorNest(TensorNest::vector_t{e.env_outputs, agent_outputs}));
 
         if (static_cast<int64_t>(e.rollout.size()) == unroll_length_ + 1) {
+          const int64_t f0 = thread_cpu_ns();
           flush_rollout(e.rollout, e.rollout_initial_state);
           TensorNest last = std::move(e.rollout.back());
           e.rollout.clear();
           e.rollout.push_back(std::move(last));
           e.rollout_initial_state = e.state_before;
+          flush_ns += thread_cpu_ns() - f0;
         }
 
         const torch::Tensor& action = agent_outputs.front();
         e.env_outputs = e.env->step(action);
         step_count_.fetch_add(1, std::memory_order_relaxed);
         issue(i);
+        ++stepped;
       }
+      const int64_t c2 = thread_cpu_ns();
+      cnt.add(kActorWait, c1 - c0);
+      cnt.add(kActorCollect, c2 - c1 - flush_ns);
+      cnt.add(kActorFlush, flush_ns);
+      cnt.rounds.fetch_add(1, std::memory_order_relaxed);
+      cnt.items.fetch_add(stepped, std::memory_order_relaxed);
+    }
+  }
+
+  // ---- rollout rows written in place (the default with a slab pool) ----
+
+  struct RowStream {
+    std::unique_ptr<EnvConnection> env;
+    TensorNest views;            // the slot carved into [T+1, 1, ...] columns
+    std::vector<uint8_t*> col;   // column base pointer per leaf
+    uint8_t* base = nullptr;     // slot base
+    int64_t t = 0;               // row whose inference is in flight / done
+    TensorNest state_before;     // agent state before row t's inference
+    TensorNest rollout_initial_state;
+  };
+
+  // The carved layout is pool-wide and learnt from the first complete step
+  // any stream sees (its env outputs and the agent outputs answering them).
+  std::shared_ptr<const RowLayout> ensure_layout(
+      const TensorNest& env_outputs, const TensorNest& agent_outputs) {
+    std::lock_guard<std::mutex> lk(layout_mu_);
+    if (!layout_) {
+      layout_ = RowLayout::make(env_outputs, agent_outputs, unroll_length_ + 1);
+    }
+    return layout_;
+  }
+
+  // Acquire a slot for `s` and carve it. Blocks on pool backpressure.
+  void acquire_row_slot(RowStream& s, const RowLayout& layout) {
+    auto slot = rollout_pool_->acquire(
+        layout.slot_bytes, [this] { return learner_queue_->is_closed(); });
+    s.base = slot.base();
+    s.col.resize(layout.leaves.size());
+    std::vector<torch::Tensor> views;
+    views.reserve(layout.leaves.size());
+    for (size_t i = 0; i < layout.leaves.size(); ++i) {
+      const RowLeaf& l = layout.leaves[i];
+      auto shape = l.shape;
+      shape[0] = layout.rows;
+      torch::Tensor v = slot.carve(shape, l.dtype);
+      s.col[i] = s.base + l.offset;
+      TORCH_CHECK(v.data_ptr() == s.col[i], "row layout / carve mismatch");
+      views.push_back(std::move(v));
+    }
+    std::vector<torch::Tensor> env_views(views.begin(),
+                                         views.begin() + layout.n_env);
+    std::vector<torch::Tensor> agent_views(views.begin() + layout.n_env,
+                                           views.end());
+    s.views = TensorNest(TensorNest::vector_t{
+        layout.env_template.pack_from(std::move(env_views)),
+        layout.agent_template.pack_from(std::move(agent_views))});
+  }
+
+  // One thread, several env streams, each filling its rollout slot in
+  // place. Requests are row PODs submitted under one lock per sweep; the
+  // thread blocks on its own mailbox, drains every ready env, steps those
+  // envs and resubmits.
+  void loop_rows(size_t lo, size_t hi) {
+    const size_t n = hi - lo;
+    const int64_t T = unroll_length_;
+    std::vector<RowStream> streams(n);
+    auto mailbox = std::make_shared<ActorMailbox>();
+    mailbox->state.assign(n, initial_agent_state_);
+    mailbox->keepalive = rollout_pool_;
+
+    // The first step of every stream travels as a nest request with a
+    // promise: its answer shows the agent-output dtypes and shapes the
+    // slots must be carved for before any row exists. Nothing is computed
+    // twice and nothing is discarded; the step becomes row 0.
+    std::vector<TensorNest> first_env(n);
+    std::vector<std::future<TensorNest>> first(n);
+    for (size_t i = 0; i < n; ++i) {
+      RowStream& s = streams[i];
+      s.env = make_env_connection(addresses_[lo + i],
+                                  seed_base_ + (int64_t)(lo + i) + 1);
+      first_env[i] = s.env->initial();
+      s.state_before = initial_agent_state_;
+      s.rollout_initial_state = initial_agent_state_;
+      first[i] = inference_batcher_->compute_async(TensorNest(
+          TensorNest::vector_t{first_env[i], initial_agent_state_}));
+    }
+    std::shared_ptr<const RowLayout> layout;
+    std::vector<int32_t> ready;
+    for (size_t i = 0; i < n; ++i) {
+      RowStream& s = streams[i];
+      TensorNest result = first[i].get();  // rethrows AsyncError
+      if (!result.is_vector() || result.vector().size() != 2) {
+        throw std::runtime_error(
+            "inference must return ((action, ...), agent_state)");
+      }
+      const TensorNest& agent_outputs = result.vector()[0];
+      mailbox->state[i] = result.vector()[1];
+      layout = ensure_layout(first_env[i], agent_outputs);
+      acquire_row_slot(s, *layout);
+      size_t leaf = 0;
+      auto store = [&](const torch::Tensor& t) {
+        if (leaf >= layout->leaves.size() || !layout->leaf_matches(leaf, t)) {
+          throw std::runtime_error(
+              "first step leaf " + std::to_string(leaf) +
+              " disagrees with the carved rollout layout");
+        }
+        torch::Tensor c = t.contiguous();
+        std::memcpy(s.col[leaf], c.data_ptr(), layout->leaves[leaf].row_bytes);
+        ++leaf;
+      };
+      first_env[i].for_each(store);
+      agent_outputs.for_each(store);
+      if (leaf != layout->leaves.size()) {
+        throw std::runtime_error("first step has too few leaves");
+      }
+      s.t = 0;
+      ready.push_back((int32_t)i);
+    }
+    first_env.clear();
+    first.clear();
+    mailbox->layout = layout;
+    const size_t n_env = layout->n_env;
+    const RowLeaf& action_leaf = layout->leaves[n_env];
+
+    CpuStageCounters& cnt = learner_queue_->actor_counters();
+    std::vector<DynamicBatcher::Request> requests;
+    std::vector<uint8_t*> leaf_ptr(n_env);
+    int64_t c0 = thread_cpu_ns();
+    try {
+      for (;;) {
+        // collect: row t of every ready stream is complete. A full rollout
+        // is enqueued as its carved views; the stream moves to a new slot
+        // whose row 0 is a copy of row T (rollouts overlap by one step).
+        int64_t flush_ns = 0;
+        for (int32_t i : ready) {
+          RowStream& s = streams[i];
+          if (s.t != T) continue;
+          const int64_t f0 = thread_cpu_ns();
+          TensorNest finished = std::move(s.views);
+          std::vector<uint8_t*> old_col = s.col;
+          acquire_row_slot(s, *layout);
+          for (size_t l = 0; l < layout->leaves.size(); ++l) {
+            const int64_t rb = layout->leaves[l].row_bytes;
+            std::memcpy(s.col[l], old_col[l] + T * rb, rb);
+          }
+          learner_queue_->enqueue(TensorNest(TensorNest::vector_t{
+              std::move(finished), s.rollout_initial_state}));
+          s.rollout_initial_state = s.state_before;
+          s.t = 0;
+          flush_ns += thread_cpu_ns() - f0;
+        }
+        const int64_t c1 = thread_cpu_ns();
+
+        // env step: answer row t's action, result lands in row t + 1.
+        for (int32_t i : ready) {
+          RowStream& s = streams[i];
+          for (size_t l = 0; l < n_env; ++l) {
+            leaf_ptr[l] = s.col[l] + (s.t + 1) * layout->leaves[l].row_bytes;
+          }
+          StepRow row{layout.get(), leaf_ptr.data(),
+                      s.col[n_env] + s.t * action_leaf.row_bytes, &action_leaf};
+          s.env->step_into(row);
+          ++s.t;
+        }
+        step_count_.fetch_add(ready.size(), std::memory_order_relaxed);
+        const int64_t c2 = thread_cpu_ns();
+
+        // issue: one request per stepped env, one lock for all of them.
+        requests.clear();
+        for (int32_t i : ready) {
+          RowStream& s = streams[i];
+          s.state_before = mailbox->state[i];
+          DynamicBatcher::Request r;
+          r.batch_size = 1;
+          r.mailbox = mailbox;
+          r.layout = layout.get();
+          r.slot_base = s.base;
+          r.row = (int32_t)s.t;
+          r.env_index = i;
+          requests.push_back(std::move(r));
+        }
+        const int64_t stepped = (int64_t)ready.size();
+        mailbox->submitted(stepped);
+        try {
+          inference_batcher_->submit_rows(requests);
+        } catch (...) {
+          mailbox->submitted(-stepped);
+          throw;
+        }
+        const int64_t c3 = thread_cpu_ns();
+
+        mailbox->wait(&ready);  // throws AsyncError for a dropped batch
+        const int64_t c4 = thread_cpu_ns();
+        cnt.add(kActorCollect, c1 - c0 - flush_ns);
+        cnt.add(kActorFlush, flush_ns);
+        cnt.add(kActorEnvStep, c2 - c1);
+        cnt.add(kActorIssue, c3 - c2);
+        cnt.add(kActorWait, c4 - c3);
+        cnt.rounds.fetch_add(1, std::memory_order_relaxed);
+        cnt.items.fetch_add(stepped, std::memory_order_relaxed);
+        c0 = c4;
+      }
+    } catch (...) {
+      // Leaving (closed queues or a failure): let consumers finish what
+      // they hold of this thread's requests first.
+      mailbox->wait_idle(std::chrono::milliseconds(2000));
+      throw;
     }
   }
 
@@ -391,6 +650,9 @@ class ActorPool {
   bool failed_ = false;
   torch::Tensor slab_frames_, slab_rew_, slab_done_;
   std::shared_ptr<PinnedSlabPool> rollout_pool_;
+  bool use_rows_ = false;
+  std::mutex layout_mu_;
+  std::shared_ptr<const RowLayout> layout_;
   std::atomic<int64_t> rollout_slot_bytes_{0};
   std::atomic<uint64_t> step_count_{0};
 };

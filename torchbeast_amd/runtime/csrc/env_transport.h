@@ -190,11 +190,59 @@ inline int connect_unix(const std::string& address,
 // Env connection interface.
 // --------------------------------------------------------------------------
 
+// Destination of one env step written in place: one raw pointer per env
+// leaf of a rollout row (queues.h: RowLayout), plus the action the step
+// answers, read from the previous row.
+struct StepRow {
+  const RowLayout* layout;
+  uint8_t* const* leaf;  // layout->n_env pointers
+  const void* action;    // first agent-output leaf of the previous row
+  const RowLeaf* action_leaf;
+
+  int64_t action_as_int() const {
+    switch (action_leaf->dtype) {
+      case torch::kInt64: return *static_cast<const int64_t*>(action);
+      case torch::kInt32: return *static_cast<const int32_t*>(action);
+      case torch::kInt16: return *static_cast<const int16_t*>(action);
+      case torch::kInt8: return *static_cast<const int8_t*>(action);
+      case torch::kUInt8: return *static_cast<const uint8_t*>(action);
+      case torch::kBool: return *static_cast<const bool*>(action) ? 1 : 0;
+      default: return action_tensor().item<int64_t>();
+    }
+  }
+  // [1, 1, ...] view of the action (what step() receives on the nest path).
+  torch::Tensor action_tensor() const {
+    return torch::from_blob(const_cast<void*>(action), action_leaf->shape,
+                            torch::TensorOptions().dtype(action_leaf->dtype));
+  }
+};
+
 class EnvConnection {
  public:
   virtual ~EnvConnection() = default;
   virtual TensorNest initial() = 0;
   virtual TensorNest step(const torch::Tensor& action) = 0;
+
+  // Step and write the result straight into a rollout row. Default: the
+  // nest step(), then one checked copy per leaf.
+  virtual void step_into(const StepRow& row) {
+    TensorNest out = step(row.action_tensor());
+    size_t i = 0;
+    out.for_each([&](const torch::Tensor& t) {
+      if (i >= row.layout->n_env || !row.layout->leaf_matches(i, t)) {
+        throw std::runtime_error(
+            "env step leaf " + std::to_string(i) +
+            " disagrees with the dtype/shape the rollout slots were carved "
+            "for");
+      }
+      torch::Tensor c = t.contiguous();
+      std::memcpy(row.leaf[i], c.data_ptr(), row.layout->leaves[i].row_bytes);
+      ++i;
+    });
+    if (i != row.layout->n_env) {
+      throw std::runtime_error("env step has too few leaves for its row");
+    }
+  }
 };
 
 inline int connect_env_socket(const std::string& address,
@@ -285,12 +333,9 @@ class NativeSyntheticEnv : public EnvConnection {
   }
 
   TensorNest step(const torch::Tensor& action) override {
-    ++episode_step_;
-    advance();
-    float reward = static_cast<float>(
-        static_cast<int64_t>((state_ + action.item<int64_t>()) % 3) - 1);
-    episode_return_ += reward;
-    bool done = episode_step_ >= spec_.episode_length;
+    float reward;
+    bool done;
+    advance_episode(action.item<int64_t>(), &reward, &done);
     TensorNest out = make_step(reward, done);
     if (done) {
       episode_step_ = 0;
@@ -299,7 +344,61 @@ class NativeSyntheticEnv : public EnvConnection {
     return out;
   }
 
+  // Same step as step(), written in place: frame bytes into the row,
+  // scalars as plain stores, no tensor allocated.
+  void step_into(const StepRow& row) override {
+    check_row(row);
+    float reward;
+    bool done;
+    advance_episode(row.action_as_int(), &reward, &done);
+    fill_frame(row.leaf[0], frame_numel_);
+    *reinterpret_cast<float*>(row.leaf[1]) = reward;
+    *reinterpret_cast<bool*>(row.leaf[2]) = done;
+    *reinterpret_cast<int32_t*>(row.leaf[3]) =
+        static_cast<int32_t>(episode_step_);
+    *reinterpret_cast<float*>(row.leaf[4]) = episode_return_;
+    if (done) {
+      episode_step_ = 0;
+      episode_return_ = 0.f;
+    }
+  }
+
  private:
+  void advance_episode(int64_t action, float* reward, bool* done) {
+    ++episode_step_;
+    advance();
+    *reward = static_cast<float>(
+        static_cast<int64_t>((state_ + action) % 3) - 1);
+    episode_return_ += *reward;
+    *done = episode_step_ >= spec_.episode_length;
+  }
+
+  // The row must be the five leaves make_step() produces; checked once per
+  // layout (the layout is fixed for a pool's lifetime).
+  void check_row(const StepRow& row) {
+    if (row.layout == checked_layout_) return;
+    frame_numel_ = 1;
+    for (auto d : spec_.shape) frame_numel_ *= d;
+    const auto& l = row.layout->leaves;
+    const bool ok = row.layout->n_env == 5 && l[0].dtype == torch::kUInt8 &&
+                    l[0].row_bytes == frame_numel_ &&
+                    l[1].dtype == torch::kFloat32 && l[1].row_bytes == 4 &&
+                    l[2].dtype == torch::kBool && l[2].row_bytes == 1 &&
+                    l[3].dtype == torch::kInt32 && l[3].row_bytes == 4 &&
+                    l[4].dtype == torch::kFloat32 && l[4].row_bytes == 4;
+    if (!ok) {
+      throw std::runtime_error(
+          "synthetic env: rollout row layout does not match its step");
+    }
+    checked_layout_ = row.layout;
+  }
+
+  void fill_frame(uint8_t* data, int64_t n) const {
+    std::memset(data, static_cast<int>(state_ & 0xFF), n);
+    uint8_t x = static_cast<uint8_t>((state_ >> 8) & 0xFF);
+    for (int64_t i = 0; i < n; i += 8) data[i] ^= x;
+  }
+
   void advance() {
     state_ ^= state_ << 13;
     state_ ^= state_ >> 7;
@@ -311,11 +410,7 @@ class NativeSyntheticEnv : public EnvConnection {
     shape.insert(shape.end(), spec_.shape.begin(), spec_.shape.end());
     torch::Tensor frame =
         torch::empty(shape, torch::TensorOptions().dtype(torch::kUInt8));
-    auto* data = frame.data_ptr<uint8_t>();
-    int64_t n = frame.numel();
-    std::memset(data, static_cast<int>(state_ & 0xFF), n);
-    uint8_t x = static_cast<uint8_t>((state_ >> 8) & 0xFF);
-    for (int64_t i = 0; i < n; i += 8) data[i] ^= x;
+    fill_frame(frame.data_ptr<uint8_t>(), frame.numel());
 
     TensorNest::vector_t fields;
     fields.emplace_back(frame);
@@ -331,6 +426,8 @@ class NativeSyntheticEnv : public EnvConnection {
   uint64_t state_;
   int64_t episode_step_ = 0;
   float episode_return_ = 0.f;
+  const RowLayout* checked_layout_ = nullptr;
+  int64_t frame_numel_ = 0;
 };
 
 inline std::unique_ptr<EnvConnection> make_env_connection(

@@ -14,6 +14,7 @@
 
 #include <ATen/cuda/CUDAContext.h>
 #include <c10/cuda/CUDAGuard.h>
+#include <hip/hip_runtime_api.h>
 #include <torch/extension.h>
 
 #include <atomic>
@@ -108,22 +109,138 @@ class InferenceRunner {
         at::cuda::getStreamFromPool(/*isHighPriority=*/true, device_.index());
     at::cuda::CUDAStreamGuard stream_guard(stream);
     torch::NoGradGuard no_grad;
+    RowStaging staging;
+    CpuMarks marks;
+    CpuStageCounters& cnt = batcher_->serve_counters();
 
     while (running_) {
       std::shared_ptr<DynamicBatcher::Batch> batch;
+      marks.begin();
       try {
         batch = batcher_->get_batch();
       } catch (const ClosedQueue&) {
-        return;
+        break;
       }
+      marks.mark(kServeBatchWait);
       try {
-        serve(*batch, stream);
+        serve(*batch, stream, staging, marks);
       } catch (const std::exception& e) {
         // Drop this batch (its promises break with AsyncError and the
         // affected actors surface it) but keep the engine serving.
         fprintf(stderr, "InferenceRunner error (batch dropped): %s\n",
                 e.what());
+        // The failed batch may have left H2D copies out of the persistent
+        // staging in flight: nothing may reuse it before they are done.
+        try {
+          stream.synchronize();
+        } catch (const std::exception& e2) {
+          fprintf(stderr, "InferenceRunner: synchronise after error: %s\n",
+                  e2.what());
+        }
       }
+      for (int i = 0; i < CpuStageCounters::kStages; ++i) {
+        cnt.add(i, marks.ns[i]);
+      }
+      cnt.rounds.fetch_add(1, std::memory_order_relaxed);
+      cnt.items.fetch_add(batch->size(), std::memory_order_relaxed);
+    }
+  }
+
+  // Per-batch CPU-time sampling for one serve thread: mark(stage) charges
+  // the CPU time since the previous sample to `stage`.
+  struct CpuMarks {
+    int64_t last = 0;
+    int64_t ns[CpuStageCounters::kStages];
+    void begin() {
+      for (auto& v : ns) v = 0;
+      last = thread_cpu_ns();
+    }
+    void mark(int stage) {
+      const int64_t now = thread_cpu_ns();
+      ns[stage] += now - last;
+      last = now;
+    }
+  };
+
+  // Persistent staging of one serve thread for row batches: allocated once
+  // for the batcher's maximum batch (rounded up to 64), reused every batch.
+  // Reuse is safe because a thread serves one batch at a time and every
+  // batch ends with a stream synchronise before its fan-out.
+  struct RowStaging {
+    int64_t cap = 0, fsz = 0, A = 0;
+    torch::Tensor h_frames, h_rew, d_frames, d_rew;  // inputs
+    torch::Tensor h_action, h_logits, h_base;        // pinned outputs
+  };
+
+  void ensure_staging(RowStaging& st, int64_t bp,
+                      const std::vector<int64_t>& chw, int64_t A) {
+    const int64_t fsz = chw[0] * chw[1] * chw[2];
+    if (st.cap >= bp && st.fsz == fsz && st.A == A &&
+        st.d_frames.size(1) == chw[0] && st.d_frames.size(2) == chw[1]) {
+      return;
+    }
+    const int64_t want = batcher_->max_batch_size();
+    int64_t cap = bp;
+    if (want <= 8192) cap = std::max(cap, (want + 63) / 64 * 64);
+    auto hopts = torch::TensorOptions().pinned_memory(true);
+    auto dopts = torch::TensorOptions().device(device_);
+    st.h_frames = torch::empty({cap, fsz}, hopts.dtype(torch::kUInt8));
+    st.h_rew = torch::empty({cap}, hopts.dtype(torch::kFloat32));
+    // Zero once: pad rows (>= b) are never written again, see serve_rows.
+    st.d_frames = torch::zeros({cap, chw[0], chw[1], chw[2]},
+                               dopts.dtype(torch::kUInt8));
+    st.d_rew = torch::zeros({cap, 1}, dopts.dtype(torch::kFloat32));
+    st.h_action = torch::empty({cap}, hopts.dtype(torch::kInt64));
+    st.h_logits = torch::empty({cap, A}, hopts.dtype(torch::kFloat32));
+    st.h_base = torch::empty({cap}, hopts.dtype(torch::kFloat32));
+    st.cap = cap;
+    st.fsz = fsz;
+    st.A = A;
+  }
+
+  // Can this batch take the allocation-free row path? Stateless model with
+  // the fused heads, every request a row of the flagship step layout.
+  bool rows_servable(const DynamicBatcher::Batch& batch) const {
+    if (!batch.all_rows() || num_lstm_layers_ != 0 || aten_only_ ||
+        legacy_serve_) {
+      return false;
+    }
+    const auto& req = batch.requests()[0];
+    const RowLayout& l = *req.layout;
+    if (!req.state().empty()) return false;
+    if (l.n_env < 3 || l.leaves.size() != l.n_env + 3) return false;
+    const auto& f = l.leaves[0];
+    const int64_t A = weights_[head_base_].size(0);
+    const auto& lv = l.leaves;
+    // The fused heads take [fc output, reward].
+    if (weights_[head_base_].size(1) != weights_[head_base_ - 2].size(0) + 1) {
+      return false;
+    }
+    return f.dtype == torch::kUInt8 && f.shape.size() == 5 &&
+           lv[1].dtype == torch::kFloat32 && lv[1].row_bytes == 4 &&
+           lv[l.n_env].dtype == torch::kInt64 && lv[l.n_env].row_bytes == 8 &&
+           lv[l.n_env + 1].dtype == torch::kFloat32 &&
+           lv[l.n_env + 1].row_bytes == 4 * A &&
+           lv[l.n_env + 2].dtype == torch::kFloat32 &&
+           lv[l.n_env + 2].row_bytes == 4 && A <= 64;
+  }
+
+  static void hip_check(hipError_t e, const char* what) {
+    TORCH_CHECK(e == hipSuccess, what, ": ", hipGetErrorString(e));
+  }
+
+  // TBAMD_SERVE_TIMINGS bookkeeping of the fused-heads paths (tensor and
+  // row): cat/gather, then forward + synchronise.
+  void record_fused_timing(int64_t cat_us, int64_t fwd_us) {
+    t_cat_us_.fetch_add(cat_us, std::memory_order_relaxed);
+    t_fwd_us_.fetch_add(fwd_us, std::memory_order_relaxed);
+    const int64_t n = timed_batches_.fetch_add(1) + 1;
+    if (n % 500 == 0) {
+      fprintf(stderr,
+              "[serve timings over %lld batches] cat=%.0fus "
+              "fwd+sync=%.0fus\n",
+              (long long)n, (double)t_cat_us_.load() / n,
+              (double)t_fwd_us_.load() / n);
     }
   }
 
@@ -134,8 +251,10 @@ class InferenceRunner {
     }
   }
 
-  void serve(DynamicBatcher::Batch& batch, at::cuda::CUDAStream& stream) {
+  void serve(DynamicBatcher::Batch& batch, at::cuda::CUDAStream& stream,
+             RowStaging& staging, CpuMarks& marks) {
     trace("begin");
+    const bool rows = rows_servable(batch);
     // Stage timers (enabled by TBAMD_SERVE_TIMINGS): cat / fwd / d2h+sync.
     const bool timing = serve_timing_;
     auto now_us = []() {
@@ -144,7 +263,8 @@ class InferenceRunner {
           .count();
     };
     int64_t t0 = timing ? now_us() : 0;
-    TensorNest inputs = batch.get_inputs();
+    TensorNest inputs;
+    if (!rows) inputs = batch.get_inputs();
     trace("cat-done");
     int64_t t_cat = timing ? now_us() : 0;
     // Serialize the FIRST forward of each quantized batch size: concurrent
@@ -175,14 +295,53 @@ class InferenceRunner {
     }
     // inputs = ((frame, reward, done, ...), state)  [classic requests]
     //        = (slot_ids, state)                     [obs-slab requests]
-    const auto& top = inputs.vector();
-    const bool slot_mode = top[0].is_leaf();
-    std::vector<torch::Tensor> state = top[1].flatten();  // [] or h,c [L,b,H]
+    const bool slot_mode = !rows && inputs.vector()[0].is_leaf();
+    std::vector<torch::Tensor> state;  // [] or h,c [L,b,H]
+    if (!rows) state = inputs.vector()[1].flatten();
     auto opts = torch::TensorOptions().device(device_);
 
     int64_t b, bp, C, H, W;
     torch::Tensor frames_p, rew, nd_gpu;
-    if (slot_mode) {
+    if (rows) {
+      // Row batch: gather each request's frame into the pinned staging (the
+      // one host copy before DMA), clamp rewards on the host while at it,
+      // then one H2D for frames and one for rewards. No tensor is
+      // allocated and no clamp / not / cast / fill kernel runs.
+      //
+      // Pad rows [b, bp) are NOT zeroed. The trunk convolves each sample
+      // on its own, fc is a row-wise GEMM and the heads kernel launches
+      // exactly b workgroups, so no row >= b ever reaches an output; and
+      // whatever a pad row holds (the zeros it was allocated with, or an
+      // older batch's frame) is a valid u8 frame, so nothing non-finite can
+      // arise from it either.
+      const auto& reqs = batch.requests();
+      const RowLayout& l = *reqs[0].layout;
+      b = (int64_t)reqs.size();
+      bp = (b + 63) / 64 * 64;
+      C = l.leaves[0].shape[2];
+      H = l.leaves[0].shape[3];
+      W = l.leaves[0].shape[4];
+      ensure_staging(staging, bp, {C, H, W}, weights_[head_base_].size(0));
+      const int64_t fsz = staging.fsz;
+      uint8_t* hf = staging.h_frames.data_ptr<uint8_t>();
+      float* hr = staging.h_rew.data_ptr<float>();
+      for (int64_t r = 0; r < b; ++r) {
+        std::memcpy(hf + r * fsz, reqs[r].leaf_ptr(0), fsz);
+        const float v = *reinterpret_cast<const float*>(reqs[r].leaf_ptr(1));
+        hr[r] = v < -1.f ? -1.f : (v > 1.f ? 1.f : v);
+      }
+      marks.mark(kServeGather);
+      if (timing) t_cat = now_us();  // gather is this path's "cat"
+      hip_check(hipMemcpyAsync(staging.d_frames.data_ptr(), hf, b * fsz,
+                               hipMemcpyHostToDevice, stream.stream()),
+                "frame H2D");
+      hip_check(hipMemcpyAsync(staging.d_rew.data_ptr(), hr, b * 4,
+                               hipMemcpyHostToDevice, stream.stream()),
+                "reward H2D");
+      frames_p = staging.d_frames.narrow(0, 0, bp);
+      rew = staging.d_rew.narrow(0, 0, bp);
+    } else if (slot_mode) {
+      const auto& top = inputs.vector();
       TORCH_CHECK(has_slab_, "slot-id request but no obs slab configured");
       const torch::Tensor ids = top[0].leaf();  // [1, b] int32
       b = ids.size(1);
@@ -196,7 +355,7 @@ class InferenceRunner {
       H = frame_shape_[1];
       W = frame_shape_[2];
     } else {
-      const auto& env = top[0].vector();
+      const auto& env = inputs.vector()[0].vector();
       const torch::Tensor frame = env[0].leaf();   // [1, b, C, H, W] u8
       const torch::Tensor reward = env[1].leaf();  // [1, b] f32
       const torch::Tensor done = env[2].leaf();    // [1, b] bool
@@ -219,6 +378,7 @@ class InferenceRunner {
       nd_gpu = (~done.reshape({b}))
                    .to(opts.dtype(torch::kFloat32), /*non_blocking=*/true);
     }
+    if (!rows) marks.mark(kServeGather);
 
     torch::Tensor x;
     if (deep_ && deep_mfma && H == 84 && W == 84 && C <= 8) {
@@ -348,12 +508,49 @@ class InferenceRunner {
       const int64_t seed =
           greedy_ ? 0 : (int64_t)(seed_ctr_.fetch_add(1) * 0x9E3779B97F4A7C15ull);
       trace("heads");
+      if (rows) {
+        fused_heads_sample_out(
+            x, rew, weights_[head_base_], weights_[head_base_ + 1],
+            weights_[head_base_ + 2], weights_[head_base_ + 3], b, greedy_,
+            seed, staging.h_action.data_ptr<int64_t>(),
+            staging.h_logits.data_ptr<float>(),
+            staging.h_base.data_ptr<float>());
+        marks.mark(kServeEnqueue);
+        stream.synchronize();
+        marks.mark(kServeSyncWait);
+        // Scatter into the rows, then wake each actor thread once.
+        const auto& reqs = batch.requests();
+        const size_t na = reqs[0].layout->n_env;
+        const int64_t A = staging.A;
+        const int64_t* ha = staging.h_action.data_ptr<int64_t>();
+        const float* hl = staging.h_logits.data_ptr<float>();
+        const float* hb = staging.h_base.data_ptr<float>();
+        for (int64_t r = 0; r < b; ++r) {
+          *reinterpret_cast<int64_t*>(reqs[r].leaf_ptr(na)) = ha[r];
+          std::memcpy(reqs[r].leaf_ptr(na + 1), hl + r * A, A * 4);
+          *reinterpret_cast<float*>(reqs[r].leaf_ptr(na + 2)) = hb[r];
+        }
+        const int64_t t_sync = timing ? now_us() : 0;
+        batch.complete_rows();
+        marks.mark(kServeFanout);
+        batcher_->count_row_batch();
+        batches_.fetch_add(1, std::memory_order_relaxed);
+        steps_.fetch_add(b, std::memory_order_relaxed);
+        if (timing) record_fused_timing(t_cat - t0, t_sync - t_cat);
+        if (warm_lock.owns_lock()) {
+          std::lock_guard<std::mutex> g(warm_mu_);
+          warmed_sizes_.insert(bq);
+        }
+        return;
+      }
       auto hs = fused_heads_sample(
           x, rew, weights_[head_base_], weights_[head_base_ + 1],
           weights_[head_base_ + 2], weights_[head_base_ + 3], b, greedy_,
           seed);
       trace("heads-sync");
+      marks.mark(kServeEnqueue);
       stream.synchronize();
+      marks.mark(kServeSyncWait);
       trace("heads-done");
       int64_t t_fwd2 = timing ? now_us() : 0;
       TensorNest::vector_t agent_out{
@@ -363,20 +560,10 @@ class InferenceRunner {
       };
       batch.set_outputs(TensorNest(TensorNest::vector_t{
           TensorNest(std::move(agent_out)), TensorNest(TensorNest::vector_t{})}));
+      marks.mark(kServeFanout);
       batches_.fetch_add(1, std::memory_order_relaxed);
       steps_.fetch_add(b, std::memory_order_relaxed);
-      if (timing) {
-        t_cat_us_.fetch_add(t_cat - t0, std::memory_order_relaxed);
-        t_fwd_us_.fetch_add(t_fwd2 - t_cat, std::memory_order_relaxed);
-        const int64_t n = timed_batches_.fetch_add(1) + 1;
-        if (n % 500 == 0) {
-          fprintf(stderr,
-                  "[serve timings over %lld batches] cat=%.0fus "
-                  "fwd+sync=%.0fus\n",
-                  (long long)n, (double)t_cat_us_.load() / n,
-                  (double)t_fwd_us_.load() / n);
-        }
-      }
+      if (timing) record_fused_timing(t_cat - t0, t_fwd2 - t_cat);
       if (warm_lock.owns_lock()) {
         std::lock_guard<std::mutex> g(warm_mu_);
         warmed_sizes_.insert(bq);
@@ -456,7 +643,9 @@ class InferenceRunner {
     torch::Tensor b_h = to_host(baseline);
     std::vector<torch::Tensor> state_h;
     for (const auto& s : new_state_gpu) state_h.push_back(to_host(s));
+    marks.mark(kServeEnqueue);
     stream.synchronize();
+    marks.mark(kServeSyncWait);
     if (timing) {
       const int64_t t_sync = now_us();
       t_cat_us_.fetch_add(t_cat - t0, std::memory_order_relaxed);
@@ -481,6 +670,7 @@ class InferenceRunner {
     for (const auto& s : state_h) state_out.emplace_back(s);
     batch.set_outputs(TensorNest(TensorNest::vector_t{
         TensorNest(std::move(agent_out)), TensorNest(std::move(state_out))}));
+    marks.mark(kServeFanout);
 
     batches_.fetch_add(1, std::memory_order_relaxed);
     steps_.fetch_add(b, std::memory_order_relaxed);
@@ -504,6 +694,11 @@ class InferenceRunner {
   // comparison in scripts/inference_speed_profiling.py).
   const bool aten_only_ = std::getenv("TBAMD_RUNNER_ATEN") != nullptr;
   const bool serve_timing_ = std::getenv("TBAMD_SERVE_TIMINGS") != nullptr;
+  // TBAMD_ACTOR_FASTPATH=0: tensor serve code only (A/B against rows).
+  const bool legacy_serve_ = [] {
+    const char* v = std::getenv("TBAMD_ACTOR_FASTPATH");
+    return v != nullptr && std::string(v) == "0";
+  }();
   std::atomic<int64_t> t_cat_us_{0}, t_fwd_us_{0}, t_d2h_us_{0};
   std::atomic<int64_t> timed_batches_{0};
   std::mutex warm_mu_;

@@ -12,6 +12,11 @@
 #include <pybind11/stl.h>
 #include <torch/extension.h>
 
+#include <unistd.h>
+
+#include <chrono>
+#include <thread>
+
 #include "actor_pool.h"
 #include "env_server.h"
 #include "inference_runner.h"
@@ -23,6 +28,66 @@ namespace py = pybind11;
 using namespace tbruntime;
 
 namespace {
+
+// ---------------------------------------------------------------------------
+// GIL release for blocking calls made from daemon threads.
+//
+// Drivers run pool.run() and the batcher/queue iterators on daemon threads
+// and exit while those threads unwind from the closed queues. A thread that
+// asks for the GIL back once the interpreter is finalizing is ended by
+// CPython with a forced stack unwind; through py::gil_scoped_release that
+// unwind starts inside a destructor and std::terminate()s the process. Rows
+// and mailboxes unwind the actor threads fast enough for a driver to reach
+// finalization while its inference threads are still on their way out, so
+// these entry points take the GIL back explicitly (outside any destructor,
+// where pybind11 lets the forced unwind pass), and a thread that finds the
+// interpreter already finalizing parks until the process exits.
+// ---------------------------------------------------------------------------
+
+inline bool python_finalizing() {
+#if PY_VERSION_HEX >= 0x030D0000
+  return Py_IsFinalizing() != 0;
+#else
+  return _Py_IsFinalizing() != 0;
+#endif
+}
+
+class DaemonGilRelease {
+ public:
+  DaemonGilRelease() : state_(PyEval_SaveThread()) {}
+  DaemonGilRelease(const DaemonGilRelease&) = delete;
+  // For a consumer that found its queue closed and drained: the driver may
+  // be about to exit, and a daemon thread that takes the GIL back now and
+  // is still tearing down its Python frames (tensor deallocation drops and
+  // retakes the GIL) when finalization starts dies the same way. Rows
+  // withdraw queued requests on close, so a driver gets from close() to
+  // exit in about a millisecond. Stay out of the interpreter for a short
+  // grace period and park if it starts finalizing meanwhile.
+  void linger_before_stop() {
+    for (int i = 0; i < 10 && !python_finalizing(); ++i) {
+      std::this_thread::sleep_for(std::chrono::milliseconds(5));
+    }
+  }
+  void reacquire() {
+    if (state_ == nullptr) return;
+    if (python_finalizing()) park();
+    PyThreadState* s = state_;
+    state_ = nullptr;
+    PyEval_RestoreThread(s);
+  }
+  // Exception path only (reacquire() was not reached).
+  ~DaemonGilRelease() {
+    if (state_ == nullptr) return;
+    if (python_finalizing()) park();
+    PyEval_RestoreThread(state_);
+  }
+
+ private:
+  [[noreturn]] static void park() {
+    for (;;) ::pause();
+  }
+  PyThreadState* state_;
+};
 
 // ---------------------------------------------------------------------------
 // nest ops over arbitrary Python object trees.
@@ -184,11 +249,12 @@ PYBIND11_MODULE(_tbruntime, m) {
       .def("__next__", [](BatchingQueue& q) {
         std::optional<TensorNest> batch;
         {
-          py::gil_scoped_release release;
+          DaemonGilRelease release;
           try {
             batch = q.dequeue_many().first;
           } catch (const ClosedQueue&) {
           }
+          release.reacquire();
         }
         if (!batch) throw py::stop_iteration();
         return *batch;
@@ -225,11 +291,13 @@ PYBIND11_MODULE(_tbruntime, m) {
       .def("__next__", [](DynamicBatcher& b) {
         std::shared_ptr<DynamicBatcher::Batch> batch;
         {
-          py::gil_scoped_release release;
+          DaemonGilRelease release;
           try {
             batch = b.get_batch();
           } catch (const ClosedQueue&) {
+            release.linger_before_stop();
           }
+          release.reacquire();
         }
         if (!batch) throw py::stop_iteration();
         return batch;
@@ -246,7 +314,12 @@ PYBIND11_MODULE(_tbruntime, m) {
            py::arg("use_obs_slab") = false,
            py::arg("rollout_budget_mb") = 0,
            py::arg("envs_per_thread") = 1)
-      .def("run", &ActorPool::run, py::call_guard<py::gil_scoped_release>())
+      .def("run",
+           [](ActorPool& pool) {
+             DaemonGilRelease release;
+             pool.run();
+             release.reacquire();
+           })
       .def("obs_slab", &ActorPool::obs_slab,
            py::call_guard<py::gil_scoped_release>())
       .def("count", &ActorPool::count);

@@ -7,6 +7,15 @@
 //   is a true DMA on a side stream, instead of pageable torch::cat output.
 // - one generic bounded MPMC queue underlies both the learner rollout queue
 //   and the inference request queue.
+// - DynamicBatcher requests come in two forms: a tensor nest plus a promise
+//   (compute()/compute_async(), the Python surface), or a ROW of a rollout
+//   slot that an actor stream fills in place (RowLayout / ActorMailbox
+//   below). Batch::get_inputs()/set_outputs() work on both; the C++ runner
+//   reads and writes rows directly and finishes with complete_rows().
+// - PinnedSlabPool slots have explicit FREE/ACQUIRED/PENDING states and a
+//   dequeue releases all its slots in one critical section.
+// - per-stage CPU-time counters of the actor and serve threads are folded
+//   into BatchingQueue::stats() / DynamicBatcher::stats().
 
 #pragma once
 
@@ -14,9 +23,13 @@
 #include <ATen/cuda/CUDAEvent.h>
 #include <torch/extension.h>
 
+#include <time.h>
+
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
+#include <cstring>
 #include <deque>
 #include <functional>
 #include <future>
@@ -52,6 +65,60 @@ struct StageStats {
     sum_us.store(0, std::memory_order_relaxed);
   }
 };
+
+// CPU time this thread has consumed so far (not wall time: a blocked thread
+// does not advance it, a spinning one does).
+inline int64_t thread_cpu_ns() {
+  timespec ts;
+  clock_gettime(CLOCK_THREAD_CPUTIME_ID, &ts);
+  return (int64_t)ts.tv_sec * 1000000000LL + ts.tv_nsec;
+}
+
+// Per-stage CPU-time totals of a group of threads (the actor threads or the
+// serve threads). Threads sample thread_cpu_ns() at stage boundaries once
+// per sweep / per batch -- never per request -- and add the differences
+// here. `items` counts env steps (actors) or requests served (serve).
+struct CpuStageCounters {
+  static constexpr int kStages = 5;
+  std::atomic<int64_t> ns[kStages];
+  std::atomic<int64_t> rounds{0};  // sweeps or batches
+  std::atomic<int64_t> items{0};
+  CpuStageCounters() { reset(); }
+  void reset() {
+    for (auto& v : ns) v.store(0, std::memory_order_relaxed);
+    rounds.store(0, std::memory_order_relaxed);
+    items.store(0, std::memory_order_relaxed);
+  }
+  void add(int stage, int64_t d) {
+    ns[stage].fetch_add(d, std::memory_order_relaxed);
+  }
+  void report(const char* prefix, const char* const* names,
+              const char* rounds_name, const char* items_name,
+              std::map<std::string, double>* out) const {
+    if (rounds.load() == 0) return;
+    for (int i = 0; i < kStages; ++i) {
+      (*out)[std::string(prefix) + "_cpu_us_" + names[i]] =
+          ns[i].load() / 1e3;
+    }
+    (*out)[std::string(prefix) + "_" + rounds_name] = (double)rounds.load();
+    (*out)[std::string(prefix) + "_" + items_name] = (double)items.load();
+  }
+};
+
+enum ActorStage { kActorEnvStep, kActorIssue, kActorWait, kActorCollect,
+                  kActorFlush };
+enum ServeStage { kServeBatchWait, kServeGather, kServeEnqueue,
+                  kServeSyncWait, kServeFanout };
+inline const char* const* actor_stage_names() {
+  static const char* const n[] = {"env_step", "issue", "wait", "collect",
+                                  "flush"};
+  return n;
+}
+inline const char* const* serve_stage_names() {
+  static const char* const n[] = {"batch_wait", "gather", "enqueue",
+                                  "sync_wait", "fanout"};
+  return n;
+}
 
 class ClosedQueue : public std::runtime_error {
  public:
@@ -102,14 +169,15 @@ inline torch::Tensor cat_pinned(const std::vector<torch::Tensor>& tensors,
 //
 // One pinned slab carved into equal rollout-sized slots (slot size fixed by
 // the first acquire; every rollout of a run has the same shape). An actor
-// acquires a slot, cats its finished rollout into slab VIEWS (so
-// .is_pinned() stays true and H2D copies stay DMA), and enqueues them.
+// stream acquires a slot up front and fills its carved VIEWS row by row
+// (the nest/promise path instead cats its finished rollout into them), so
+// .is_pinned() stays true and H2D copies stay DMA, and enqueues them.
 // Rollout tensors never escape the learner-side BatchingQueue (both
 // assembly modes produce fresh batched outputs), so slot recycling is
 // driven by the queue alone: after assembling a batch it calls
-// mark_consumed(ptr, event) per source leaf, and the slot returns to the
-// free list once that dequeue's copy event has completed (immediately in
-// CPU mode). acquire() blocks when the budget is exhausted — this is the
+// mark_consumed_many(leaf pointers, event) once, and each slot returns to
+// the free list once that dequeue's copy event has completed (immediately
+// in CPU mode). acquire() blocks when the budget is exhausted — this is the
 // backpressure that bounds rollout memory to the configured budget
 // (BASELINE.json north star: buffering sized against a memory budget, not
 // unbounded ad-hoc allocations).
@@ -125,6 +193,10 @@ class PinnedSlabPool {
     PinnedSlabPool* pool;
     int64_t index;
     int64_t used = 0;
+
+    uint8_t* base() const {
+      return pool->slab_.data_ptr<uint8_t>() + index * pool->slot_bytes_;
+    }
 
     torch::Tensor carve(std::vector<int64_t> shape, torch::ScalarType dtype) {
       int64_t numel = 1;
@@ -154,6 +226,7 @@ class PinnedSlabPool {
               .dtype(torch::kUInt8)
               .pinned_memory(pinned_memory_wanted()));
       for (int64_t i = slots - 1; i >= 0; --i) free_.push_back(i);
+      state_.assign(slots, SlotState::FREE);
       total_slots_ = slots;
     }
     TORCH_CHECK(slot_bytes <= slot_bytes_,
@@ -163,6 +236,8 @@ class PinnedSlabPool {
       if (!free_.empty()) {
         const int64_t idx = free_.back();
         free_.pop_back();
+        state_[idx] = SlotState::ACQUIRED;
+        ++held_;
         return Slot{this, idx, 0};
       }
       backpressure_waits_.fetch_add(1, std::memory_order_relaxed);
@@ -173,23 +248,49 @@ class PinnedSlabPool {
     }
   }
 
-  // Consumer-side: `ptr` was read by copies whose completion `ev` tracks
-  // (ev == nullptr for synchronous CPU assembly). Idempotent per slot per
-  // dequeue: all leaves of a rollout carry the same event.
+  // Consumer-side: the slot holding `ptr` was read by copies whose
+  // completion `ev` tracks (ev == nullptr for synchronous CPU assembly).
+  // One call per slot: a second call for the same slot could land after the
+  // slot was freed and re-acquired and would free it under its new owner.
+  // A consumer that sees several pointers into one slot (the leaves of a
+  // rollout) uses mark_consumed_many instead.
   void mark_consumed(const void* ptr,
                      const std::shared_ptr<at::cuda::CUDAEvent>& ev) {
+    mark_consumed_many({ptr}, ev);
+  }
+
+  // Release every slot that one dequeue read, in ONE critical section over
+  // the unique slot indices, so a slot cannot be freed, handed to another
+  // actor and then freed again by a later leaf of the same dequeue.
+  // Pointers outside the slab are ignored.
+  void mark_consumed_many(const std::vector<const void*>& ptrs,
+                          const std::shared_ptr<at::cuda::CUDAEvent>& ev) {
     std::lock_guard<std::mutex> lk(mu_);
     if (!slab_.defined()) return;
     const uint8_t* base = slab_.data_ptr<uint8_t>();
-    const auto* p = static_cast<const uint8_t*>(ptr);
-    if (p < base || p >= base + total_slots_ * slot_bytes_) return;
-    const int64_t idx = (p - base) / slot_bytes_;
-    if (ev == nullptr) {
-      if (!in_list(free_, idx)) free_.push_back(idx);
-    } else if (!in_pending(idx)) {
-      pending_.emplace_back(idx, ev);
+    std::vector<int64_t> idxs;
+    idxs.reserve(ptrs.size());
+    for (const void* ptr : ptrs) {
+      const auto* p = static_cast<const uint8_t*>(ptr);
+      if (p < base || p >= base + total_slots_ * slot_bytes_) continue;
+      idxs.push_back((p - base) / slot_bytes_);
     }
-    cv_.notify_all();
+    std::sort(idxs.begin(), idxs.end());
+    idxs.erase(std::unique(idxs.begin(), idxs.end()), idxs.end());
+    for (int64_t idx : idxs) {
+      // Only a slot somebody holds can be released; FREE or PENDING here
+      // means it was released already.
+      if (state_[idx] != SlotState::ACQUIRED) continue;
+      --held_;
+      if (ev == nullptr) {
+        state_[idx] = SlotState::FREE;
+        free_.push_back(idx);
+      } else {
+        state_[idx] = SlotState::PENDING;
+        pending_.emplace_back(idx, ev);
+      }
+    }
+    if (!idxs.empty()) cv_.notify_all();
   }
 
   bool manages(const void* ptr) const {
@@ -207,26 +308,22 @@ class PinnedSlabPool {
     out["slab_slot_bytes"] = (double)slot_bytes_;
     out["slab_free"] = (double)free_.size();
     out["slab_pending"] = (double)pending_.size();
+    out["slab_held"] = (double)held_;
     out["slab_backpressure_waits"] = (double)backpressure_waits_.load();
     return out;
   }
 
  private:
-  static bool in_list(const std::vector<int64_t>& v, int64_t x) {
-    for (auto e : v) {
-      if (e == x) return true;
-    }
-    return false;
-  }
-  bool in_pending(int64_t idx) const {
-    for (const auto& p : pending_) {
-      if (p.first == idx) return true;
-    }
-    return false;
-  }
+  // FREE: on free_. ACQUIRED: held by an actor (filling) or travelling
+  // through the learner queue. PENDING: read by H2D copies still in
+  // flight; freed at reap time. A slot is freed only from ACQUIRED (no
+  // event) or from PENDING (reap).
+  enum class SlotState : uint8_t { FREE, ACQUIRED, PENDING };
+
   void reap_pending() {
     for (auto it = pending_.begin(); it != pending_.end();) {
       if (it->second->query()) {
+        state_[it->first] = SlotState::FREE;
         free_.push_back(it->first);
         it = pending_.erase(it);
       } else {
@@ -243,6 +340,8 @@ class PinnedSlabPool {
   int64_t slot_bytes_ = 0;
   int64_t total_slots_ = 0;
   std::vector<int64_t> free_;
+  std::vector<SlotState> state_;
+  int64_t held_ = 0;
   std::vector<std::pair<int64_t, std::shared_ptr<at::cuda::CUDAEvent>>>
       pending_;
   std::atomic<int64_t> backpressure_waits_{0};
@@ -307,6 +406,24 @@ class BoundedQueue {
     not_empty_.notify_one();
   }
 
+  // Enqueue several items under one lock acquisition and one wake-up (the
+  // consumer that drains only part of the queue wakes the next one, see
+  // dequeue_many). A bounded queue may overshoot its bound by one call.
+  void enqueue_many(std::vector<Item>& items) {
+    if (items.empty()) return;
+    {
+      std::unique_lock<std::mutex> lock(mu_);
+      not_full_.wait(lock, [this] {
+        return closed_ || !max_size_ ||
+               static_cast<int64_t>(items_.size()) < *max_size_;
+      });
+      if (closed_) throw ClosedQueue("enqueue to closed queue");
+      for (auto& item : items) items_.push_back(std::move(item));
+    }
+    items.clear();
+    not_empty_.notify_one();
+  }
+
   // Block until at least min_n items (or timeout with >=1, or close).
   // Returns up to max_n items. Throws ClosedQueue when closed and drained.
   std::vector<Item> dequeue_many(int64_t min_n, int64_t max_n,
@@ -335,8 +452,11 @@ class BoundedQueue {
       out.push_back(std::move(items_.front()));
       items_.pop_front();
     }
+    const bool leftover = !items_.empty();
     lock.unlock();
     not_full_.notify_all();
+    // enqueue_many wakes one consumer for many items: pass the wake on.
+    if (leftover) not_empty_.notify_one();
     return out;
   }
 
@@ -358,6 +478,30 @@ class BoundedQueue {
   bool is_closed() const {
     std::lock_guard<std::mutex> lock(mu_);
     return closed_;
+  }
+
+  // close(), and in the same critical section remove and return the queued
+  // items `pred` selects.
+  template <typename Pred>
+  std::vector<Item> close_and_take(Pred pred) {
+    std::vector<Item> taken;
+    {
+      std::lock_guard<std::mutex> lock(mu_);
+      if (closed_) throw ClosedQueue("queue was already closed");
+      closed_ = true;
+      std::deque<Item> kept;
+      for (auto& item : items_) {
+        if (pred(item)) {
+          taken.push_back(std::move(item));
+        } else {
+          kept.push_back(std::move(item));
+        }
+      }
+      items_.swap(kept);
+    }
+    not_empty_.notify_all();
+    not_full_.notify_all();
+    return taken;
   }
 
  private:
@@ -396,6 +540,7 @@ class BatchingQueue {
                            std::chrono::milliseconds(*timeout_ms))
                      : std::nullopt),
         check_inputs_(check_inputs),
+        max_queue_size_(maximum_queue_size),
         queue_(maximum_queue_size) {
     if (min_batch_size_ < 1) {
       throw std::invalid_argument("Min batch size must be >= 1");
@@ -458,20 +603,12 @@ class BatchingQueue {
       });
       if (source_pool_) {
         // Slab-pooled rollout slots recycle once the H2D copies complete.
-        for (const auto* n : ptrs) {
-          n->for_each([this, &ev](const torch::Tensor& t) {
-            source_pool_->mark_consumed(t.data_ptr(), ev);
-          });
-        }
+        source_pool_->mark_consumed_many(leaf_pointers(ptrs), ev);
       }
     } else {
       batched = batch_nests(ptrs, batch_dim_);
       if (source_pool_) {
-        for (const auto* n : ptrs) {
-          n->for_each([this](const torch::Tensor& t) {
-            source_pool_->mark_consumed(t.data_ptr(), nullptr);
-          });
-        }
+        source_pool_->mark_consumed_many(leaf_pointers(ptrs), nullptr);
       }
     }
     auto result = std::make_pair(std::move(batched),
@@ -484,9 +621,17 @@ class BatchingQueue {
   int64_t size() const { return queue_.size(); }
   void close() { queue_.close(); }
   bool is_closed() const { return queue_.is_closed(); }
+  std::optional<int64_t> max_queue_size() const { return max_queue_size_; }
+  int64_t max_batch_size() const { return max_batch_size_; }
+
+  // CPU-time counters of the actor threads feeding this queue (they show
+  // up in stats() so a driver that prints stats() prints them too).
+  CpuStageCounters& actor_counters() { return actor_counters_; }
 
   std::map<std::string, double> stats() const {
     std::map<std::string, double> out;
+    actor_counters_.report("actor", actor_stage_names(), "sweeps",
+                           "env_steps", &out);
     out["dequeues"] = wait_stats_.n.load();
     if (wait_stats_.n > 0) {
       out["avg_wait_ms"] = wait_stats_.sum_us / 1e3 / wait_stats_.n;
@@ -506,25 +651,172 @@ class BatchingQueue {
   void reset_stats() {
     wait_stats_.reset();
     cat_stats_.reset();
+    actor_counters_.reset();
   }
 
  private:
+  static std::vector<const void*> leaf_pointers(
+      const std::vector<const TensorNest*>& nests) {
+    std::vector<const void*> out;
+    for (const auto* n : nests) {
+      n->for_each(
+          [&out](const torch::Tensor& t) { out.push_back(t.data_ptr()); });
+    }
+    return out;
+  }
+
   const std::optional<torch::Device> output_device_;
   const int64_t batch_dim_;
   const int64_t min_batch_size_;
   const int64_t max_batch_size_;
   const std::optional<std::chrono::milliseconds> timeout_;
   const bool check_inputs_;
+  const std::optional<int64_t> max_queue_size_;
   BoundedQueue<TensorNest> queue_;
   std::shared_ptr<PinnedSlabPool> source_pool_;
   std::unique_ptr<at::cuda::CUDAStream> copy_stream_;
   mutable StageStats wait_stats_;
   mutable StageStats cat_stats_;
+  CpuStageCounters actor_counters_;
 };
 
 // ---------------------------------------------------------------------------
 // DynamicBatcher: many blocking compute() callers -> one batched inference.
 // ---------------------------------------------------------------------------
+
+// ---------------------------------------------------------------------------
+// Rollout rows and completion mailboxes (the actor fast path).
+//
+// An env stream that fills its rollout in place owns one pinned slot carved
+// into [T+1, 1, ...] columns, one per env leaf and per agent-output leaf.
+// Step t is a ROW of every column: a raw pointer plus a row-byte size. An
+// inference request for such a step is a small POD (slot base, row, layout,
+// mailbox, env index) instead of a tensor nest plus a promise; whoever
+// serves it reads the env leaves from the row, writes the agent outputs
+// into the same row and posts the env index to the owning actor thread's
+// mailbox -- one lock and at most one wake per actor thread per batch.
+// ---------------------------------------------------------------------------
+
+struct RowLeaf {
+  std::vector<int64_t> shape;  // one step, leading [1, 1, ...] included
+  torch::ScalarType dtype;
+  int64_t row_bytes;
+  int64_t offset;  // of the column inside the slot (256-byte aligned)
+};
+
+struct RowLayout {
+  TensorNest env_template;    // structure of one step's env outputs
+  TensorNest agent_template;  // structure of one step's agent outputs
+  std::vector<RowLeaf> leaves;  // env leaves first, then agent leaves
+  size_t n_env = 0;
+  int64_t rows = 0;  // T + 1
+  int64_t slot_bytes = 0;
+
+  static RowLeaf describe(const torch::Tensor& t) {
+    TORCH_CHECK(t.dim() >= 1 && t.size(0) == 1,
+                "rollout rows need step leaves with a leading time dim of 1, "
+                "got shape ", t.sizes());
+    RowLeaf l;
+    l.shape = t.sizes().vec();
+    l.dtype = t.scalar_type();
+    l.row_bytes = t.numel() * (int64_t)t.element_size();
+    l.offset = 0;
+    return l;
+  }
+
+  static std::shared_ptr<RowLayout> make(const TensorNest& env_outputs,
+                                         const TensorNest& agent_outputs,
+                                         int64_t rows) {
+    auto out = std::make_shared<RowLayout>();
+    out->env_template = env_outputs;
+    out->agent_template = agent_outputs;
+    out->rows = rows;
+    env_outputs.for_each(
+        [&](const torch::Tensor& t) { out->leaves.push_back(describe(t)); });
+    out->n_env = out->leaves.size();
+    agent_outputs.for_each(
+        [&](const torch::Tensor& t) { out->leaves.push_back(describe(t)); });
+    int64_t used = 0;
+    for (auto& l : out->leaves) {
+      // Same packing as PinnedSlabPool::Slot::carve.
+      l.offset = (used + 255) & ~int64_t(255);
+      used = l.offset + rows * l.row_bytes;
+    }
+    out->slot_bytes = used + 4096;
+    // The templates only give structure; do not keep the first step alive.
+    auto drop = [](const torch::Tensor&) { return torch::Tensor(); };
+    out->env_template = out->env_template.map(drop);
+    out->agent_template = out->agent_template.map(drop);
+    return out;
+  }
+
+  bool leaf_matches(size_t i, const torch::Tensor& t) const {
+    const RowLeaf& l = leaves[i];
+    return t.scalar_type() == l.dtype && t.sizes().vec() == l.shape;
+  }
+};
+
+// Completion queue of one actor thread, shared with every request of that
+// thread still in flight (so a serve thread can never post into a dead
+// actor thread's memory). state[i] is env i's agent state: read by the
+// server as the request's input state, replaced by the new state before i
+// is posted to `ready`.
+struct ActorMailbox {
+  std::mutex mu;
+  std::condition_variable cv;
+  std::vector<int32_t> ready;
+  enum Failure { kNone, kAsync, kClosed };
+  Failure failed = kNone;
+  std::string error;
+  std::vector<TensorNest> state;
+  std::shared_ptr<const RowLayout> layout;
+  std::shared_ptr<void> keepalive;  // the slab the rows point into
+
+  int64_t outstanding = 0;  // requests submitted and not yet answered
+
+  void submitted(int64_t n) {
+    std::lock_guard<std::mutex> lk(mu);
+    outstanding += n;
+  }
+  void post(const int32_t* idx, size_t n) {
+    {
+      std::lock_guard<std::mutex> lk(mu);
+      ready.insert(ready.end(), idx, idx + n);
+      outstanding -= (int64_t)n;
+    }
+    cv.notify_one();
+  }
+  // An unwinding actor thread waits (bounded) until nobody works on its
+  // requests any more, so that when ActorPool::run() returns no consumer is
+  // still computing an answer for this pool.
+  void wait_idle(std::chrono::milliseconds limit) {
+    std::unique_lock<std::mutex> lk(mu);
+    cv.wait_for(lk, limit, [this] { return outstanding <= 0; });
+  }
+  // The first failure wins. kAsync: a batch was dropped (AsyncError);
+  // kClosed: the batcher was closed under the request (ClosedQueue).
+  void fail(const std::string& what, Failure kind, int64_t n_requests = 1) {
+    {
+      std::lock_guard<std::mutex> lk(mu);
+      outstanding -= n_requests;
+      if (failed == kNone) {
+        failed = kind;
+        error = what;
+      }
+    }
+    cv.notify_all();
+  }
+  // Blocks (no polling) until completions or a failure arrive; swaps the
+  // ready indices into `out`.
+  void wait(std::vector<int32_t>* out) {
+    out->clear();
+    std::unique_lock<std::mutex> lk(mu);
+    cv.wait(lk, [this] { return failed != kNone || !ready.empty(); });
+    if (failed == kAsync) throw AsyncError(error);
+    if (failed == kClosed) throw ClosedQueue(error);
+    out->swap(ready);
+  }
+};
 
 class DynamicBatcher {
  public:
@@ -532,6 +824,29 @@ class DynamicBatcher {
     TensorNest inputs;
     int64_t batch_size;  // along batch_dim
     std::shared_ptr<std::promise<TensorNest>> promise;
+    // Row form (promise == nullptr, inputs unused): see ActorMailbox.
+    std::shared_ptr<ActorMailbox> mailbox;
+    const RowLayout* layout = nullptr;
+    uint8_t* slot_base = nullptr;
+    int32_t row = 0;
+    int32_t env_index = 0;
+
+    bool is_row() const { return mailbox != nullptr; }
+    uint8_t* leaf_ptr(size_t leaf) const {
+      const RowLeaf& l = layout->leaves[leaf];
+      return slot_base + l.offset + (int64_t)row * l.row_bytes;
+    }
+    const TensorNest& state() const { return mailbox->state[env_index]; }
+    // The env leaves of the row as a [1, 1, ...] nest of views.
+    TensorNest env_nest() const {
+      std::vector<torch::Tensor> leaves;
+      for (size_t i = 0; i < layout->n_env; ++i) {
+        const RowLeaf& l = layout->leaves[i];
+        leaves.push_back(torch::from_blob(
+            leaf_ptr(i), l.shape, torch::TensorOptions().dtype(l.dtype)));
+      }
+      return layout->env_template.pack_from(std::move(leaves));
+    }
   };
 
   class Batch {
@@ -542,17 +857,30 @@ class DynamicBatcher {
           requests_(std::move(requests)),
           check_outputs_(check_outputs),
           service_stats_(service_stats),
-          created_us_(now_us()) {}
+          created_us_(now_us()) {
+      for (const auto& r : requests_) {
+        if (r.is_row()) {
+          ++n_rows_;
+          if (r.layout != requests_[0].layout) uniform_rows_ = false;
+        }
+      }
+    }
 
     ~Batch() {
       if (!fulfilled_) {
-        auto eptr = std::make_exception_ptr(
-            AsyncError("Batch destroyed before set_outputs was called"));
+        const char* what = "Batch destroyed before set_outputs was called";
+        auto eptr = std::make_exception_ptr(AsyncError(what));
         // fulfilled_count_ promises already carry values (set_outputs threw
         // mid-way); breaking those again would raise future_error out of a
         // destructor, so only fail the rest.
         for (size_t i = fulfilled_count_; i < requests_.size(); ++i) {
-          requests_[i].promise->set_exception(eptr);
+          if (requests_[i].promise) requests_[i].promise->set_exception(eptr);
+        }
+        // Row requests are posted only once everything succeeded, so none
+        // of them has been answered: every owning actor thread gets the
+        // error (it throws AsyncError out of its wait).
+        for (const auto& r : requests_) {
+          if (r.is_row()) r.mailbox->fail(what, ActorMailbox::kAsync);
         }
       }
     }
@@ -563,10 +891,31 @@ class DynamicBatcher {
       return total;
     }
 
+    // True when every request is a row of one layout: the C++ runner then
+    // gathers and scatters rows itself (requests(), complete_rows()).
+    bool all_rows() const {
+      return n_rows_ == requests_.size() && uniform_rows_ && n_rows_ > 0;
+    }
+    const std::vector<Request>& requests() const { return requests_; }
+
     TensorNest get_inputs() {
+      if (all_rows() && batch_dim_ <= 1) return gather_rows();
+      // Nest requests, or a mix (start-up, when some streams still send
+      // their first step as a nest): rows join as [1, 1, ...] views.
+      std::vector<TensorNest> row_nests;
+      row_nests.reserve(n_rows_);
+      for (const auto& r : requests_) {
+        if (r.is_row()) {
+          row_nests.push_back(
+              TensorNest(TensorNest::vector_t{r.env_nest(), r.state()}));
+        }
+      }
       std::vector<const TensorNest*> ptrs;
       ptrs.reserve(requests_.size());
-      for (const auto& r : requests_) ptrs.push_back(&r.inputs);
+      size_t k = 0;
+      for (const auto& r : requests_) {
+        ptrs.push_back(r.is_row() ? &row_nests[k++] : &r.inputs);
+      }
       return batch_nests(ptrs, batch_dim_);
     }
 
@@ -606,10 +955,52 @@ class DynamicBatcher {
             }));
         offset += req.batch_size;
       }
+      if (n_rows_ > 0) {
+        // Validate every row request's slice against its carved columns
+        // before writing any: a mismatch throws here, the batch stays
+        // unfulfilled and its destructor fails the actors loudly.
+        for (size_t i = 0; i < requests_.size(); ++i) {
+          if (requests_[i].is_row()) check_row_slice(requests_[i], slices[i]);
+        }
+        for (size_t i = 0; i < requests_.size(); ++i) {
+          if (requests_[i].is_row()) scatter_row(requests_[i], slices[i]);
+        }
+      }
       for (size_t i = 0; i < requests_.size(); ++i) {
-        requests_[i].promise->set_value(std::move(slices[i]));
+        if (requests_[i].promise) {
+          requests_[i].promise->set_value(std::move(slices[i]));
+        }
         fulfilled_count_ = i + 1;
       }
+      complete_rows();
+    }
+
+    // Post every row request to its actor thread (grouped: one lock and one
+    // wake per mailbox) and mark the batch served. The caller has written
+    // the agent outputs into the rows and the new states into the
+    // mailboxes. set_outputs() ends with this; the C++ runner calls it
+    // directly after scattering rows itself.
+    void complete_rows() {
+      if (fulfilled_) throw std::runtime_error("batch completed twice");
+      if (n_rows_ > 0) {
+        std::vector<std::pair<ActorMailbox*, int32_t>> order;
+        order.reserve(n_rows_);
+        for (const auto& r : requests_) {
+          if (r.is_row()) order.emplace_back(r.mailbox.get(), r.env_index);
+        }
+        std::sort(order.begin(), order.end());
+        std::vector<int32_t> idx;
+        for (size_t i = 0; i < order.size();) {
+          size_t j = i;
+          idx.clear();
+          for (; j < order.size() && order[j].first == order[i].first; ++j) {
+            idx.push_back(order[j].second);
+          }
+          order[i].first->post(idx.data(), idx.size());
+          i = j;
+        }
+      }
+      fulfilled_count_ = requests_.size();
       fulfilled_ = true;
       if (service_stats_ != nullptr) {
         service_stats_->add(now_us() - created_us_);
@@ -617,11 +1008,87 @@ class DynamicBatcher {
     }
 
    private:
+    // One output tensor per leaf, filled by copying each request's row; no
+    // per-request tensor. Needs batch_dim <= 1 (step leaves are [1, 1, ...],
+    // so the batched leaf is the rows back to back).
+    TensorNest gather_rows() {
+      const RowLayout& layout = *requests_[0].layout;
+      const int64_t b = (int64_t)requests_.size();
+      std::vector<torch::Tensor> leaves;
+      leaves.reserve(layout.n_env);
+      for (size_t i = 0; i < layout.n_env; ++i) {
+        const RowLeaf& l = layout.leaves[i];
+        TORCH_CHECK((int64_t)l.shape.size() > batch_dim_ &&
+                        l.shape[batch_dim_] == 1,
+                    "row leaf has no batch dimension of size 1");
+        auto shape = l.shape;
+        shape[batch_dim_] = b;
+        auto opts = torch::TensorOptions().dtype(l.dtype);
+        // Same pinning rule as cat_pinned.
+        if (pinned_memory_wanted() && b * l.row_bytes >= 65536) {
+          opts = opts.pinned_memory(true);
+        }
+        torch::Tensor out = torch::empty(shape, opts);
+        auto* dst = static_cast<uint8_t*>(out.data_ptr());
+        for (int64_t r = 0; r < b; ++r) {
+          std::memcpy(dst + r * l.row_bytes, requests_[r].leaf_ptr(i),
+                      l.row_bytes);
+        }
+        leaves.push_back(std::move(out));
+      }
+      std::vector<const TensorNest*> states;
+      states.reserve(requests_.size());
+      for (const auto& r : requests_) states.push_back(&r.state());
+      return TensorNest(TensorNest::vector_t{
+          layout.env_template.pack_from(std::move(leaves)),
+          batch_nests(states, batch_dim_)});
+    }
+
+    static const TensorNest& agent_part(const TensorNest& slice) {
+      if (!slice.is_vector() || slice.vector().size() != 2) {
+        throw std::invalid_argument(
+            "inference must return ((action, ...), agent_state)");
+      }
+      return slice.vector()[0];
+    }
+
+    void check_row_slice(const Request& req, const TensorNest& slice) const {
+      const RowLayout& layout = *req.layout;
+      size_t i = layout.n_env;
+      agent_part(slice).for_each([&](const torch::Tensor& t) {
+        if (i >= layout.leaves.size() || !layout.leaf_matches(i, t)) {
+          throw std::invalid_argument(
+              "agent output leaf " + std::to_string(i - layout.n_env) +
+              " disagrees with the dtype/shape the rollout slots were "
+              "carved for");
+        }
+        ++i;
+      });
+      if (i != layout.leaves.size()) {
+        throw std::invalid_argument(
+            "agent outputs have fewer leaves than the rollout slots were "
+            "carved for");
+      }
+    }
+
+    void scatter_row(const Request& req, const TensorNest& slice) {
+      const RowLayout& layout = *req.layout;
+      size_t i = layout.n_env;
+      agent_part(slice).for_each([&](const torch::Tensor& t) {
+        torch::Tensor c = t.is_cuda() ? t.cpu() : t.contiguous();
+        std::memcpy(req.leaf_ptr(i), c.data_ptr(), layout.leaves[i].row_bytes);
+        ++i;
+      });
+      req.mailbox->state[req.env_index] = slice.vector()[1];
+    }
+
     const int64_t batch_dim_;
     std::vector<Request> requests_;
     const bool check_outputs_;
     StageStats* service_stats_;
     const int64_t created_us_;
+    size_t n_rows_ = 0;
+    bool uniform_rows_ = true;
     bool fulfilled_ = false;
     size_t fulfilled_count_ = 0;
   };
@@ -668,6 +1135,23 @@ class DynamicBatcher {
     return future;
   }
 
+  // Row requests of one actor thread: one lock acquisition for all of them.
+  // `requests` is emptied.
+  void submit_rows(std::vector<Request>& requests) {
+    queue_.enqueue_many(requests);
+  }
+
+  int64_t max_batch_size() const { return max_batch_size_; }
+
+  // CPU-time counters of the threads serving this batcher.
+  CpuStageCounters& serve_counters() { return serve_counters_; }
+
+  // Batches the C++ runner served on its row path (rows read and written in
+  // place, persistent staging) rather than through get_inputs/set_outputs.
+  void count_row_batch() {
+    row_batches_.fetch_add(1, std::memory_order_relaxed);
+  }
+
   TensorNest compute(TensorNest inputs) {
     const int64_t t0 = now_us();
     std::future<TensorNest> future = compute_async(std::move(inputs));
@@ -693,11 +1177,26 @@ class DynamicBatcher {
   }
 
   int64_t size() const { return queue_.size(); }
-  void close() { queue_.close(); }
+
+  // Queued nest requests stay for the consumers to drain, as before. Queued
+  // row requests are withdrawn and their actor threads told at once: such a
+  // thread ends at its next submit anyway, so serving them is wasted work,
+  // and a thread whose requests nobody serves any more (consumers gone)
+  // would otherwise sit in its mailbox forever.
+  void close() {
+    std::vector<Request> rows =
+        queue_.close_and_take([](const Request& r) { return r.is_row(); });
+    for (const auto& r : rows) {
+      r.mailbox->fail("inference batcher closed", ActorMailbox::kClosed);
+    }
+  }
   bool is_closed() const { return queue_.is_closed(); }
 
   std::map<std::string, double> stats() const {
     std::map<std::string, double> out;
+    serve_counters_.report("serve", serve_stage_names(), "batches",
+                           "requests", &out);
+    out["serve_row_batches"] = (double)row_batches_.load();
     out["computes"] = roundtrip_stats_.n.load();
     out["batches"] = batch_size_stats_.n.load();
     if (roundtrip_stats_.n > 0) {
@@ -721,6 +1220,8 @@ class DynamicBatcher {
     formation_stats_.reset();
     batch_size_stats_.reset();
     service_stats_.reset();
+    serve_counters_.reset();
+    row_batches_.store(0, std::memory_order_relaxed);
   }
 
  private:
@@ -734,6 +1235,8 @@ class DynamicBatcher {
   mutable StageStats formation_stats_;
   mutable StageStats service_stats_;
   mutable StageStats batch_size_stats_;  // sum_us field holds summed sizes
+  CpuStageCounters serve_counters_;
+  std::atomic<int64_t> row_batches_{0};
 };
 
 }  // namespace tbruntime

@@ -21,4 +21,14 @@ std::vector<torch::Tensor> fused_heads_sample(torch::Tensor x,
                                               torch::Tensor base_b, int64_t b,
                                               bool greedy, int64_t seed);
 
+// Same kernel, results written into caller-owned pinned host buffers
+// (action [b], logits [b, A], baseline [b]); allocates nothing.
+void fused_heads_sample_out(const torch::Tensor& x, const torch::Tensor& rew,
+                            const torch::Tensor& policy_w,
+                            const torch::Tensor& policy_b,
+                            const torch::Tensor& base_w,
+                            const torch::Tensor& base_b, int64_t b,
+                            bool greedy, int64_t seed, int64_t* out_action,
+                            float* out_logits, float* out_baseline);
+
 }  // namespace tbruntime

@@ -20,6 +20,8 @@
 
 #include <vector>
 
+#include "runtime_kernels.h"
+
 namespace tbruntime {
 
 namespace {
@@ -181,11 +183,7 @@ std::vector<torch::Tensor> fused_heads_sample(torch::Tensor x,
                                               torch::Tensor base_w,
                                               torch::Tensor base_b, int64_t b,
                                               bool greedy, int64_t seed) {
-  const int D = x.size(1);
   const int A = policy_w.size(0);
-  TORCH_CHECK(A <= 64, "heads kernel supports up to 64 actions");
-  TORCH_CHECK(policy_w.size(1) == D + 1 && base_w.size(1) == D + 1,
-              "head weights must take [x, reward]");
   // Allocate pinned outputs at the quantized batch size (cache-friendly;
   // ragged sizes would hipHostMalloc + device-sync per serve), then hand
   // back narrowed views.
@@ -196,16 +194,34 @@ std::vector<torch::Tensor> fused_heads_sample(torch::Tensor x,
       torch::empty({bq, A}, hopts.dtype(torch::kFloat32)).narrow(0, 0, b);
   auto baseline =
       torch::empty({bq}, hopts.dtype(torch::kFloat32)).narrow(0, 0, b);
+  fused_heads_sample_out(x, rew, policy_w, policy_b, base_w, base_b, b, greedy,
+                         seed, action.data_ptr<int64_t>(),
+                         logits.data_ptr<float>(), baseline.data_ptr<float>());
+  return {action, logits, baseline};
+}
+
+void fused_heads_sample_out(const torch::Tensor& x, const torch::Tensor& rew,
+                            const torch::Tensor& policy_w,
+                            const torch::Tensor& policy_b,
+                            const torch::Tensor& base_w,
+                            const torch::Tensor& base_b, int64_t b,
+                            bool greedy, int64_t seed, int64_t* out_action,
+                            float* out_logits, float* out_baseline) {
+  const int D = x.size(1);
+  const int A = policy_w.size(0);
+  TORCH_CHECK(A <= 64, "heads kernel supports up to 64 actions");
+  TORCH_CHECK(policy_w.size(1) == D + 1 && base_w.size(1) == D + 1,
+              "head weights must take [x, reward]");
+  TORCH_CHECK(b >= 1 && x.size(0) >= b && rew.numel() >= b,
+              "heads kernel: batch exceeds its inputs");
   const size_t lds = (size_t)(D + 1) * sizeof(float);
   hipLaunchKernelGGL(heads_sample_kernel, dim3((uint32_t)b), dim3(256), lds,
                      at::cuda::getCurrentCUDAStream(), x.data_ptr<float>(),
                      rew.data_ptr<float>(), policy_w.data_ptr<float>(),
                      policy_b.data_ptr<float>(), base_w.data_ptr<float>(),
                      base_b.data_ptr<float>(), (int)b, D, A,
-                     (uint64_t)seed, greedy ? 1 : 0,
-                     action.data_ptr<int64_t>(), logits.data_ptr<float>(),
-                     baseline.data_ptr<float>());
-  return {action, logits, baseline};
+                     (uint64_t)seed, greedy ? 1 : 0, out_action, out_logits,
+                     out_baseline);
 }
 
 }  // namespace tbruntime
