@@ -23,6 +23,7 @@
 #include "nest.h"
 #include "nest_pybind.h"
 #include "queues.h"
+#include "runtime_kernels.h"
 
 namespace py = pybind11;
 using namespace tbruntime;
@@ -192,6 +193,34 @@ py::object nest_map_many(const py::function& f, const py::args& nests) {
   return nest_pack_as(first, mapped);
 }
 
+// unpack_rollouts_host() over tensors, same surface as the kernel's test
+// binding: uint8 [outer, B, inner_bytes] outputs.
+std::vector<torch::Tensor> unpack_rollouts_host_tensors(
+    torch::Tensor staging, int64_t stride, int64_t B,
+    std::vector<std::tuple<int64_t, int64_t, int64_t>> columns) {
+  TORCH_CHECK(staging.device().is_cpu() &&
+                  staging.scalar_type() == torch::kUInt8 &&
+                  staging.is_contiguous(),
+              "staging must be a contiguous uint8 CPU tensor");
+  TORCH_CHECK(B >= 1 && stride >= 1 && staging.numel() >= B * stride,
+              "staging smaller than B * stride");
+  std::vector<torch::Tensor> out;
+  std::vector<UnpackColumn> desc;
+  for (const auto& c : columns) {
+    const int64_t off = std::get<0>(c), outer = std::get<1>(c),
+                  inner = std::get<2>(c);
+    TORCH_CHECK(off >= 0 && outer >= 1 && inner >= 1 &&
+                    off + outer * inner <= stride,
+                "column overruns the staging row");
+    out.push_back(torch::empty({outer, B, inner}, staging.options()));
+    desc.push_back(
+        UnpackColumn{off, inner, outer, out.back().data_ptr<uint8_t>()});
+  }
+  unpack_rollouts_host(staging.data_ptr<uint8_t>(), stride, B, desc.data(),
+                       (int)desc.size());
+  return out;
+}
+
 py::object nest_front(const py::object& n) {
   py::list flat = nest_flatten(n);
   if (flat.size() == 0) throw NestError("front() of empty nest");
@@ -223,6 +252,19 @@ PYBIND11_MODULE(_tbruntime, m) {
   m.def("flatten", &nest_flatten, py::arg("nest"));
   m.def("pack_as", &nest_pack_as, py::arg("nest"), py::arg("sequence"));
   m.def("front", &nest_front, py::arg("nest"));
+
+  // ---- rollout unpack kernel ----
+  // GPU-output BatchingQueues reach the kernel through this hook (the
+  // queue headers are also built into programs without any kernel).
+  set_unpack_hook(&launch_unpack_rollouts);
+  // Test-only: the kernel on a caller-made staging buffer; `columns` is a
+  // list of (src_off, outer, inner_bytes).
+  m.def("unpack_rollouts", &unpack_rollouts, py::arg("staging"),
+        py::arg("stride"), py::arg("B"), py::arg("columns"));
+  // Its oracle: the host reference unpack on a CPU staging tensor.
+  m.def("unpack_rollouts_host", &unpack_rollouts_host_tensors,
+        py::arg("staging"), py::arg("stride"), py::arg("B"),
+        py::arg("columns"));
 
   // ---- BatchingQueue ----
   py::class_<BatchingQueue, std::shared_ptr<BatchingQueue>>(m, "BatchingQueue")

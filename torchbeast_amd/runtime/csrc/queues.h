@@ -16,11 +16,15 @@
 //   dequeue releases all its slots in one critical section.
 // - per-stage CPU-time counters of the actor and serve threads are folded
 //   into BatchingQueue::stats() / DynamicBatcher::stats().
+// - a GPU-output BatchingQueue fed from a PinnedSlabPool assembles a batch
+//   with one DMA per rollout slot plus one unpack kernel (rollout_gather.h)
+//   instead of one strided copy per rollout and leaf.
 
 #pragma once
 
 #include <ATen/cuda/CUDAContext.h>
 #include <ATen/cuda/CUDAEvent.h>
+#include <hip/hip_runtime_api.h>
 #include <torch/extension.h>
 
 #include <time.h>
@@ -41,6 +45,7 @@
 #include <vector>
 
 #include "nest.h"
+#include "rollout_gather.h"
 
 namespace tbruntime {
 
@@ -301,6 +306,15 @@ class PinnedSlabPool {
     return p >= base && p < base + total_slots_ * slot_bytes_;
   }
 
+  // Where the slots lie (all zero before the first acquire); fixed from
+  // then on.
+  SlabGeometry geometry() const {
+    std::lock_guard<std::mutex> lk(mu_);
+    if (!slab_.defined()) return SlabGeometry();
+    return SlabGeometry{slab_.data_ptr<uint8_t>(), slot_bytes_,
+                        total_slots_ * slot_bytes_};
+  }
+
   std::map<std::string, double> stats() const {
     std::lock_guard<std::mutex> lk(mu_);
     std::map<std::string, double> out;
@@ -361,25 +375,30 @@ inline TensorNest batch_nests(const std::vector<const TensorNest*>& nests,
 // interleave with inference traffic, and eliminates the host-side memcpy
 // entirely (the "rollouts DMA straight into the learner" design,
 // SURVEY.md §2.2).
+inline torch::Tensor copy_column_to_device(
+    const std::vector<torch::Tensor>& column, int64_t batch_dim,
+    torch::Device device) {
+  auto shape = column[0].sizes().vec();
+  int64_t total = 0;
+  for (const auto& t : column) total += t.size(batch_dim);
+  shape[batch_dim] = total;
+  torch::Tensor out = torch::empty(shape, column[0].options().device(device));
+  int64_t offset = 0;
+  for (const auto& t : column) {
+    out.narrow(batch_dim, offset, t.size(batch_dim))
+        .copy_(t, /*non_blocking=*/true);
+    offset += t.size(batch_dim);
+  }
+  return out;
+}
+
 inline TensorNest batch_nests_to_device(
     const std::vector<const TensorNest*>& nests, int64_t batch_dim,
     torch::Device device) {
   return TensorNest::apply_columns(
       nests,
       [batch_dim, device](const std::vector<torch::Tensor>& column) {
-        auto shape = column[0].sizes().vec();
-        int64_t total = 0;
-        for (const auto& t : column) total += t.size(batch_dim);
-        shape[batch_dim] = total;
-        torch::Tensor out =
-            torch::empty(shape, column[0].options().device(device));
-        int64_t offset = 0;
-        for (const auto& t : column) {
-          out.narrow(batch_dim, offset, t.size(batch_dim))
-              .copy_(t, /*non_blocking=*/true);
-          offset += t.size(batch_dim);
-        }
-        return out;
+        return copy_column_to_device(column, batch_dim, device);
       });
 }
 
@@ -552,6 +571,9 @@ class BatchingQueue {
     if (maximum_queue_size && *maximum_queue_size < 1) {
       throw std::invalid_argument("Max queue size must be >= 1");
     }
+    // TBAMD_QUEUE_GATHER=0 keeps the per-leaf copies for every batch (A/B).
+    const char* g = std::getenv("TBAMD_QUEUE_GATHER");
+    gather_enabled_ = !(g != nullptr && std::string(g) == "0");
   }
 
   int64_t batch_dim() const { return batch_dim_; }
@@ -588,9 +610,14 @@ class BatchingQueue {
       }
       at::cuda::CUDAStream current =
           at::cuda::getCurrentCUDAStream(output_device_->index());
+      // Set by the gather path once nothing enqueued later reads a slot.
+      std::shared_ptr<at::cuda::CUDAEvent> release_ev;
       {
         at::cuda::CUDAStreamGuard guard(*copy_stream_);
-        batched = batch_nests_to_device(ptrs, batch_dim_, *output_device_);
+        if (!(gather_enabled_ && source_pool_ && unpack_hook() != nullptr &&
+              gather_to_device(ptrs, &batched, &release_ev))) {
+          batched = batch_nests_to_device(ptrs, batch_dim_, *output_device_);
+        }
       }
       auto ev = std::make_shared<at::cuda::CUDAEvent>();
       ev->record(*copy_stream_);
@@ -603,7 +630,8 @@ class BatchingQueue {
       });
       if (source_pool_) {
         // Slab-pooled rollout slots recycle once the H2D copies complete.
-        source_pool_->mark_consumed_many(leaf_pointers(ptrs), ev);
+        source_pool_->mark_consumed_many(leaf_pointers(ptrs),
+                                         release_ev ? release_ev : ev);
       }
     } else {
       batched = batch_nests(ptrs, batch_dim_);
@@ -640,6 +668,10 @@ class BatchingQueue {
     if (source_pool_) {
       for (const auto& kv : source_pool_->stats()) out[kv.first] = kv.second;
     }
+    // Dequeues assembled by slot DMA + unpack kernel, and the leaf
+    // positions they gathered (the rest took the per-leaf copies).
+    out["gather_dequeues"] = (double)gather_dequeues_.load();
+    out["gather_columns"] = (double)gather_columns_.load();
     return out;
   }
 
@@ -652,9 +684,95 @@ class BatchingQueue {
     wait_stats_.reset();
     cat_stats_.reset();
     actor_counters_.reset();
+    gather_dequeues_.store(0, std::memory_order_relaxed);
+    gather_columns_.store(0, std::memory_order_relaxed);
   }
 
  private:
+  // Batch assembly from whole slots (rollout_gather.h), on the current
+  // (copy) stream: one DMA per item from its slot window into its staging
+  // row, one unpack kernel into a single output arena, and the per-leaf
+  // copies for the positions that are no slab column. Returns false, with
+  // nothing enqueued, when the plan is empty. *release_ev is set when the
+  // slots may be recycled as soon as the DMAs are done.
+  bool gather_to_device(const std::vector<const TensorNest*>& nests,
+                        TensorNest* batched,
+                        std::shared_ptr<at::cuda::CUDAEvent>* release_ev) {
+    std::vector<std::vector<torch::Tensor>> flats;
+    flats.reserve(nests.size());
+    for (const auto* n : nests) flats.push_back(n->flatten());
+    const SlabGeometry geom = source_pool_->geometry();
+    const GatherPlan plan = plan_gather(flats, batch_dim_, geom);
+    if (plan.empty()) return false;
+    const UnpackHook unpack = unpack_hook();
+    at::cuda::CUDAStream stream =
+        at::cuda::getCurrentCUDAStream(output_device_->index());
+
+    // Does a position left to the per-leaf copies read slot memory? Then
+    // the slots are released by the caller's event, after those copies.
+    bool fallback_reads_slab = false;
+    for (size_t i = 0; i < plan.gathered.size(); ++i) {
+      if (plan.gathered[i]) continue;
+      for (const auto& f : flats) {
+        if (f[i].defined() && f[i].device().is_cpu() &&
+            geom.contains(f[i].data_ptr())) {
+          fallback_reads_slab = true;
+        }
+      }
+    }
+
+    GatherOutputs outputs;
+    {
+      // Several learner threads may dequeue at once; the staging buffer is
+      // shared, so one batch's DMAs and its kernel are enqueued together.
+      std::lock_guard<std::mutex> lk(gather_mu_);
+      const int64_t stride = plan.stride();
+      // Persistent staging: grown only when a larger batch arrives. It is
+      // written and read on the copy stream alone, so reuse is safe by
+      // stream order: the next batch's DMAs queue up behind this batch's
+      // unpack kernel (and a replaced buffer goes back to the allocator
+      // on the same stream).
+      if (!staging_.defined() || staging_.numel() < plan.B * stride) {
+        staging_ = torch::empty({plan.B * stride},
+                                torch::TensorOptions()
+                                    .dtype(torch::kUInt8)
+                                    .device(*output_device_));
+      }
+      auto* staging = staging_.data_ptr<uint8_t>();
+      for (int64_t b = 0; b < plan.B; ++b) {
+        const hipError_t err = hipMemcpyAsync(
+            staging + b * stride, plan.window_start[b], plan.win_bytes,
+            hipMemcpyHostToDevice, stream.stream());
+        TORCH_CHECK(err == hipSuccess, "rollout gather: hipMemcpyAsync: ",
+                    hipGetErrorString(err));
+      }
+      if (!fallback_reads_slab) {
+        // The last read of any slot: recycle them before the unpack runs.
+        *release_ev = std::make_shared<at::cuda::CUDAEvent>();
+        (*release_ev)->record(stream);
+      }
+      outputs = make_gather_outputs(plan, *output_device_);
+      unpack(staging, stride, plan.B, outputs.columns.data(),
+             (int)outputs.columns.size());
+    }
+
+    std::vector<torch::Tensor> leaves(plan.gathered.size());
+    for (size_t c = 0; c < plan.columns.size(); ++c) {
+      leaves[plan.columns[c].leaf] = std::move(outputs.leaves[c]);
+    }
+    std::vector<torch::Tensor> column(flats.size());
+    for (size_t i = 0; i < leaves.size(); ++i) {
+      if (plan.gathered[i]) continue;
+      for (size_t b = 0; b < flats.size(); ++b) column[b] = flats[b][i];
+      leaves[i] = copy_column_to_device(column, batch_dim_, *output_device_);
+    }
+    *batched = nests[0]->pack_from(std::move(leaves));
+    gather_dequeues_.fetch_add(1, std::memory_order_relaxed);
+    gather_columns_.fetch_add((int64_t)plan.columns.size(),
+                              std::memory_order_relaxed);
+    return true;
+  }
+
   static std::vector<const void*> leaf_pointers(
       const std::vector<const TensorNest*>& nests) {
     std::vector<const void*> out;
@@ -675,6 +793,11 @@ class BatchingQueue {
   BoundedQueue<TensorNest> queue_;
   std::shared_ptr<PinnedSlabPool> source_pool_;
   std::unique_ptr<at::cuda::CUDAStream> copy_stream_;
+  bool gather_enabled_ = true;
+  std::mutex gather_mu_;
+  torch::Tensor staging_;  // device, B x window; see gather_to_device
+  std::atomic<int64_t> gather_dequeues_{0};
+  std::atomic<int64_t> gather_columns_{0};
   mutable StageStats wait_stats_;
   mutable StageStats cat_stats_;
   CpuStageCounters actor_counters_;

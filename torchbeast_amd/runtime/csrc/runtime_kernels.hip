@@ -12,12 +12,18 @@
 // logits, baseline and a Gumbel-argmax action sample in ONE kernel,
 // writing results directly into pinned host output buffers (no separate
 // D2H copies). Replaces ~12 ATen ops per serve.
+//
+// unpack_rollouts: the learner queue's batch assembly. B rollout slots are
+// DMAed whole into a staging buffer; this kernel transposes them into the
+// [T+1, B, ...] leaves in one launch (rollout_gather.h has the layout).
 
 #include <ATen/cuda/CUDAContext.h>
+#include <c10/cuda/CUDAGuard.h>
 #include <hip/hip_runtime.h>
 #include <hiprand/hiprand_kernel.h>
 #include <torch/extension.h>
 
+#include <tuple>
 #include <vector>
 
 #include "runtime_kernels.h"
@@ -136,9 +142,166 @@ __global__ __launch_bounds__(256) void heads_sample_kernel(
   }
 }
 
+// unpack_rollouts: staging [B, stride] holds one rollout slot window per
+// row; column c has `outer` rows of `inner_bytes` at src_off in every
+// staging row. Output row (o, b) of a column goes to
+// dst + (o * B + b) * inner_bytes, i.e. the [outer, B, inner] leaf.
+//
+// Workgroups are dealt to columns on the host (block_begin): a wide column
+// (inner_bytes >= kWideRowBytes) gets one workgroup per output row, the
+// lanes striding over the row; a narrow one gets one lane per output row.
+// Either way the only division is one 32-bit (row / B) per workgroup or
+// per lane, never per element. The access width (16, 8, 4 or 1 bytes) is
+// the widest that divides the row length, the staging stride and both base
+// addresses; it is uniform over a column.
+// Limitation: the two paths are sized for the rollout slot's columns, frame
+// rows of tens of KB and leaves of a few bytes. A row of 256..4095 bytes
+// keeps only inner_bytes/16 of the workgroup's 256 lanes busy (16 lanes at
+// 256 bytes), and a row of up to 255 bytes is copied serially by one lane
+// with uncoalesced accesses. Both are correct but far below bandwidth; a
+// mid-width column (LSTM-sized state, say) moved into the slab would want a
+// wavefront-per-row path first.
+constexpr int kUnpackThreads = 256;
+constexpr int64_t kWideRowBytes = 256;
+
+struct UnpackArgs {
+  UnpackColumn col[kMaxGatherColumns];
+  uint32_t block_begin[kMaxGatherColumns + 1];
+  int32_t n_cols;
+  int32_t B;
+  int64_t stride;
+};
+
+template <typename V>
+__device__ __forceinline__ void copy_strided(uint8_t* __restrict__ dst,
+                                             const uint8_t* __restrict__ src,
+                                             int64_t nbytes, int first,
+                                             int step) {
+  const int n = (int)(nbytes / (int64_t)sizeof(V));
+  auto* d = reinterpret_cast<V*>(dst);
+  const auto* s = reinterpret_cast<const V*>(src);
+  for (int i = first; i < n; i += step) d[i] = s[i];
+}
+
+__device__ __forceinline__ void copy_row(uint8_t* dst, const uint8_t* src,
+                                         int64_t nbytes, unsigned align,
+                                         int first, int step) {
+  if ((align & 15u) == 0) {
+    copy_strided<uint4>(dst, src, nbytes, first, step);
+  } else if ((align & 7u) == 0) {
+    copy_strided<uint2>(dst, src, nbytes, first, step);
+  } else if ((align & 3u) == 0) {
+    copy_strided<uint32_t>(dst, src, nbytes, first, step);
+  } else {
+    copy_strided<uint8_t>(dst, src, nbytes, first, step);
+  }
+}
+
+__global__ __launch_bounds__(kUnpackThreads) void unpack_rollouts_kernel(
+    const uint8_t* __restrict__ staging, const UnpackArgs args) {
+  int c = 0;
+  while (c + 1 < args.n_cols && blockIdx.x >= args.block_begin[c + 1]) ++c;
+  const UnpackColumn col = args.col[c];
+  const uint32_t local = blockIdx.x - args.block_begin[c];
+  const uint32_t B = (uint32_t)args.B;
+  const uint32_t rows = (uint32_t)col.outer * B;
+  const uint8_t* src0 = staging + col.src_off;
+  const unsigned align =
+      (unsigned)(((uint64_t)col.inner_bytes | (uint64_t)args.stride |
+                  (uint64_t)(uintptr_t)src0 | (uint64_t)(uintptr_t)col.dst) &
+                 15u);
+  if (col.inner_bytes >= kWideRowBytes) {
+    const uint32_t row = local;  // one workgroup per output row
+    if (row >= rows) return;
+    const uint32_t o = row / B, b = row - o * B;
+    copy_row(col.dst + (int64_t)row * col.inner_bytes,
+             src0 + (int64_t)b * args.stride + (int64_t)o * col.inner_bytes,
+             col.inner_bytes, align, (int)threadIdx.x, kUnpackThreads);
+  } else {
+    const uint32_t row = local * kUnpackThreads + threadIdx.x;
+    if (row >= rows) return;
+    const uint32_t o = row / B, b = row - o * B;
+    copy_row(col.dst + (int64_t)row * col.inner_bytes,
+             src0 + (int64_t)b * args.stride + (int64_t)o * col.inner_bytes,
+             col.inner_bytes, align, 0, 1);
+  }
+}
+
 }  // namespace
 
 // Host wrappers -------------------------------------------------------------
+
+void launch_unpack_rollouts(const uint8_t* staging, int64_t stride, int64_t B,
+                            const UnpackColumn* columns, int n_columns) {
+  TORCH_CHECK(n_columns >= 1 && n_columns <= kMaxGatherColumns,
+              "unpack_rollouts: 1..", kMaxGatherColumns, " columns");
+  TORCH_CHECK(B >= 1 && stride >= 1, "unpack_rollouts: empty batch");
+  UnpackArgs args;
+  args.n_cols = n_columns;
+  args.B = (int32_t)B;
+  args.stride = stride;
+  int64_t blocks = 0;
+  for (int c = 0; c < n_columns; ++c) {
+    const UnpackColumn& col = columns[c];
+    TORCH_CHECK(col.inner_bytes >= 1 && col.inner_bytes < (int64_t(1) << 31) &&
+                    col.outer >= 1 && col.src_off >= 0 && col.dst != nullptr,
+                "unpack_rollouts: bad column ", c);
+    TORCH_CHECK(col.src_off + col.outer * col.inner_bytes <= stride,
+                "unpack_rollouts: column ", c, " overruns the staging row");
+    const int64_t rows = col.outer * B;
+    TORCH_CHECK(rows < (int64_t(1) << 31), "unpack_rollouts: too many rows");
+    args.col[c] = col;
+    args.block_begin[c] = (uint32_t)blocks;
+    blocks += col.inner_bytes >= kWideRowBytes
+                  ? rows
+                  : (rows + kUnpackThreads - 1) / kUnpackThreads;
+    TORCH_CHECK(blocks < (int64_t(1) << 31), "unpack_rollouts: grid too big");
+  }
+  for (int c = n_columns; c <= kMaxGatherColumns; ++c) {
+    args.block_begin[c] = (uint32_t)blocks;
+  }
+  for (int c = n_columns; c < kMaxGatherColumns; ++c) {
+    args.col[c] = UnpackColumn{0, 0, 0, nullptr};
+  }
+  hipLaunchKernelGGL(unpack_rollouts_kernel, dim3((uint32_t)blocks),
+                     dim3(kUnpackThreads), 0,
+                     at::cuda::getCurrentCUDAStream(), staging, args);
+  const hipError_t err = hipGetLastError();
+  TORCH_CHECK(err == hipSuccess, "unpack_rollouts launch: ",
+              hipGetErrorString(err));
+}
+
+std::vector<torch::Tensor> unpack_rollouts(
+    torch::Tensor staging, int64_t stride, int64_t B,
+    std::vector<std::tuple<int64_t, int64_t, int64_t>> columns) {
+  TORCH_CHECK(staging.is_cuda() && staging.scalar_type() == torch::kUInt8 &&
+                  staging.is_contiguous(),
+              "unpack_rollouts: staging must be a contiguous uint8 GPU tensor");
+  TORCH_CHECK(B >= 1 && stride >= 1 && staging.numel() >= B * stride,
+              "unpack_rollouts: staging smaller than B * stride");
+  at::cuda::CUDAGuard device_guard(staging.device());
+  int64_t total = 0;
+  for (const auto& c : columns) {
+    TORCH_CHECK(std::get<1>(c) >= 1 && std::get<2>(c) >= 1,
+                "unpack_rollouts: empty column");
+    total += round_up_256(std::get<1>(c) * B * std::get<2>(c));
+  }
+  torch::Tensor arena = torch::empty({total}, staging.options());
+  std::vector<UnpackColumn> desc;
+  std::vector<torch::Tensor> out;
+  int64_t off = 0;
+  for (const auto& c : columns) {
+    const int64_t outer = std::get<1>(c), inner = std::get<2>(c);
+    const int64_t nbytes = outer * B * inner;
+    desc.push_back(UnpackColumn{std::get<0>(c), inner, outer,
+                                arena.data_ptr<uint8_t>() + off});
+    out.push_back(arena.narrow(0, off, nbytes).view({outer, B, inner}));
+    off += round_up_256(nbytes);
+  }
+  launch_unpack_rollouts(staging.data_ptr<uint8_t>(), stride, B, desc.data(),
+                         (int)desc.size());
+  return out;
+}
 
 // Returns {frames [bp,C,H,W] u8 (GPU), rew [bp,1] f32 (GPU), nd [bp] f32}.
 std::vector<torch::Tensor> gather_obs(torch::Tensor slab_frames,
