@@ -8,15 +8,18 @@
 // with a rollout is the state *before* the inference of its first step.
 //
 // Two implementations:
-// - loop_rows (default whenever the pool has a rollout budget and is not in
-//   obs-slab mode): every env stream holds a pinned slab slot carved into
-//   [T+1, 1, ...] columns and fills it row by row in place. Envs write their
+// - loop_rows (default whenever the pool has a rollout budget; in obs-slab
+//   mode only for a stateless agent, whose batches the runner then gathers
+//   from the rows on the GPU): every env stream holds a pinned slab slot
+//   carved into [T+1, 1, ...] columns and fills it row by row in place.
+//   Envs write their
 //   step into the row (EnvConnection::step_into), requests are row PODs
 //   submitted under one lock per sweep, and the thread blocks on its own
 //   ActorMailbox (queues.h) -- no per-step tensors, promises or polling. A
 //   finished rollout is enqueued as the carved views.
-// - loop / loop_multi (no rollout budget, obs-slab mode, or
-//   TBAMD_ACTOR_FASTPATH=0 for A/B runs): per-step nests, promise/future
+// - loop / loop_multi (no rollout budget, obs-slab mode with a recurrent
+//   agent, or TBAMD_ACTOR_FASTPATH=0 for A/B runs): per-step nests (slot
+//   ids into a second pinned slab in obs-slab mode), promise/future
 //   requests, rollouts cat-ed at flush time.
 
 #pragma once
@@ -91,22 +94,30 @@ class ActorPool {
     }
     // TBAMD_ACTOR_FASTPATH=0 keeps the nest/promise loops below (A/B only).
     const char* fp = std::getenv("TBAMD_ACTOR_FASTPATH");
-    use_rows_ = rollout_pool_ != nullptr && !use_obs_slab_ &&
-                !(fp != nullptr && std::string(fp) == "0");
+    const bool fastpath = !(fp != nullptr && std::string(fp) == "0");
+    // Obs-slab mode has a row form for stateless agents: the frame is
+    // written once, into its rollout row, and the runner gathers the batch
+    // from the rows on the GPU (RowLayout::device_gather). No second slab,
+    // no slot ids. A recurrent agent on rows would fall back to a host
+    // gather of its frames, so it keeps the slot-id loops.
+    device_gather_ = use_obs_slab_ && rollout_pool_ != nullptr && fastpath &&
+                     initial_agent_state_.empty();
+    use_rows_ = rollout_pool_ != nullptr && fastpath &&
+                (!use_obs_slab_ || device_gather_);
   }
 
   // Pinned observation slab (slot per actor). Valid once the first env has
   // produced an observation; the inference runner gathers from it by slot
-  // id instead of cat-ing per-request frame tensors.
+  // id instead of cat-ing per-request frame tensors. Empty (at once) when
+  // the pool is not in obs-slab mode or takes the row form, which has no
+  // such slab.
   std::vector<torch::Tensor> obs_slab() {
+    if (device_gather_ || !use_obs_slab_) return {};
     std::unique_lock<std::mutex> lk(slab_mu_);
-    slab_cv_.wait(lk, [this] {
-      return slab_ready_ || failed_ || !use_obs_slab_;
-    });
+    slab_cv_.wait(lk, [this] { return slab_ready_ || failed_; });
     if (failed_ && !slab_ready_) {
       throw std::runtime_error("actor pool failed before producing obs");
     }
-    if (!use_obs_slab_) return {};
     return {slab_frames_, slab_rew_, slab_done_};
   }
 
@@ -348,7 +359,10 @@ class ActorPool {
       const TensorNest& env_outputs, const TensorNest& agent_outputs) {
     std::lock_guard<std::mutex> lk(layout_mu_);
     if (!layout_) {
-      layout_ = RowLayout::make(env_outputs, agent_outputs, unroll_length_ + 1);
+      auto layout =
+          RowLayout::make(env_outputs, agent_outputs, unroll_length_ + 1);
+      layout->device_gather = device_gather_;
+      layout_ = std::move(layout);
     }
     return layout_;
   }
@@ -389,7 +403,7 @@ class ActorPool {
     std::vector<RowStream> streams(n);
     auto mailbox = std::make_shared<ActorMailbox>();
     mailbox->state.assign(n, initial_agent_state_);
-    mailbox->keepalive = rollout_pool_;
+    mailbox->slab = rollout_pool_;
 
     // The first step of every stream travels as a nest request with a
     // promise: its answer shows the agent-output dtypes and shapes the
@@ -651,6 +665,7 @@ class ActorPool {
   torch::Tensor slab_frames_, slab_rew_, slab_done_;
   std::shared_ptr<PinnedSlabPool> rollout_pool_;
   bool use_rows_ = false;
+  bool device_gather_ = false;  // obs-slab mode on rows, see the constructor
   std::mutex layout_mu_;
   std::shared_ptr<const RowLayout> layout_;
   std::atomic<int64_t> rollout_slot_bytes_{0};

@@ -7,6 +7,10 @@
 //   get_batch -> pinned-host cat -> H2D on a dedicated HIP stream ->
 //   AtariNet forward (ATen ops; custom fused kernels swap in at the op
 //   level) -> sampled action -> D2H -> set_outputs.
+// Row batches (requests that are rows of rollout slots) skip the cat: their
+// frames are gathered into persistent staging either on the host (one
+// memcpy per frame, then one H2D) or, in obs-slab mode, by gather_rows_kernel
+// reading the rows over the host link.
 // Behavior-model weights are VIEWS of the learner's flat actor buffer, so
 // weight sync stays one flat device copy with no runner involvement.
 
@@ -166,16 +170,24 @@ class InferenceRunner {
   // for the batcher's maximum batch (rounded up to 64), reused every batch.
   // Reuse is safe because a thread serves one batch at a time and every
   // batch ends with a stream synchronise before its fan-out.
+  // With device_gather the host side of the inputs is only the pointer
+  // table the gather kernel reads ([2, cap] addresses: frames, rewards);
+  // h_frames ([cap, fsz] pinned, ~100 MB for full-resolution frames at cap
+  // 1024) and h_rew are then not allocated.
   struct RowStaging {
     int64_t cap = 0, fsz = 0, A = 0;
+    bool device_gather = false;
     torch::Tensor h_frames, h_rew, d_frames, d_rew;  // inputs
+    torch::Tensor h_table;                           // pinned, device gather
     torch::Tensor h_action, h_logits, h_base;        // pinned outputs
   };
 
   void ensure_staging(RowStaging& st, int64_t bp,
-                      const std::vector<int64_t>& chw, int64_t A) {
+                      const std::vector<int64_t>& chw, int64_t A,
+                      bool device_gather) {
     const int64_t fsz = chw[0] * chw[1] * chw[2];
     if (st.cap >= bp && st.fsz == fsz && st.A == A &&
+        st.device_gather == device_gather &&
         st.d_frames.size(1) == chw[0] && st.d_frames.size(2) == chw[1]) {
       return;
     }
@@ -184,8 +196,16 @@ class InferenceRunner {
     if (want <= 8192) cap = std::max(cap, (want + 63) / 64 * 64);
     auto hopts = torch::TensorOptions().pinned_memory(true);
     auto dopts = torch::TensorOptions().device(device_);
-    st.h_frames = torch::empty({cap, fsz}, hopts.dtype(torch::kUInt8));
-    st.h_rew = torch::empty({cap}, hopts.dtype(torch::kFloat32));
+    if (device_gather) {
+      st.h_table = torch::zeros({2, cap}, hopts.dtype(torch::kInt64));
+      st.h_frames = torch::Tensor();
+      st.h_rew = torch::Tensor();
+    } else {
+      st.h_frames = torch::empty({cap, fsz}, hopts.dtype(torch::kUInt8));
+      st.h_rew = torch::empty({cap}, hopts.dtype(torch::kFloat32));
+      st.h_table = torch::Tensor();
+    }
+    st.device_gather = device_gather;
     // Zero once: pad rows (>= b) are never written again, see serve_rows.
     st.d_frames = torch::zeros({cap, chw[0], chw[1], chw[2]},
                                dopts.dtype(torch::kUInt8));
@@ -313,7 +333,8 @@ class InferenceRunner {
       // exactly b workgroups, so no row >= b ever reaches an output; and
       // whatever a pad row holds (the zeros it was allocated with, or an
       // older batch's frame) is a valid u8 frame, so nothing non-finite can
-      // arise from it either.
+      // arise from it either. The same holds for the device gather below:
+      // its kernel writes rows [0, b) of d_frames / d_rew and nothing else.
       const auto& reqs = batch.requests();
       const RowLayout& l = *reqs[0].layout;
       b = (int64_t)reqs.size();
@@ -321,23 +342,56 @@ class InferenceRunner {
       C = l.leaves[0].shape[2];
       H = l.leaves[0].shape[3];
       W = l.leaves[0].shape[4];
-      ensure_staging(staging, bp, {C, H, W}, weights_[head_base_].size(0));
+      // Device gather: the GPU reads each frame and reward from its row in
+      // the pinned rollout slab (large frames, where the host copy below is
+      // what bounds the serve thread). Needs host addresses the GPU can
+      // read, i.e. a pinned slab.
+      const auto& pool = reqs[0].mailbox->slab;
+      const bool device_gather =
+          (row_gather_ == kRowGatherAuto ? l.device_gather
+                                         : row_gather_ == kRowGatherDevice) &&
+          pool != nullptr && pool->is_pinned();
+      ensure_staging(staging, bp, {C, H, W}, weights_[head_base_].size(0),
+                     device_gather);
       const int64_t fsz = staging.fsz;
-      uint8_t* hf = staging.h_frames.data_ptr<uint8_t>();
-      float* hr = staging.h_rew.data_ptr<float>();
-      for (int64_t r = 0; r < b; ++r) {
-        std::memcpy(hf + r * fsz, reqs[r].leaf_ptr(0), fsz);
-        const float v = *reinterpret_cast<const float*>(reqs[r].leaf_ptr(1));
-        hr[r] = v < -1.f ? -1.f : (v > 1.f ? 1.f : v);
+      if (device_gather) {
+        // One layout per batch means one pool per batch. The table is
+        // written only here, and only with addresses checked against the
+        // slab: a stray one would be a GPU fault.
+        const SlabGeometry slab = pool->geometry();
+        int64_t* table = staging.h_table.data_ptr<int64_t>();
+        auto** ft = reinterpret_cast<const uint8_t**>(table);
+        auto** rt = reinterpret_cast<const float**>(table + staging.cap);
+        build_row_table(
+            b, [&reqs](int64_t r) { return reqs[r].leaf_ptr(0); },
+            [&reqs](int64_t r) { return reqs[r].leaf_ptr(1); }, fsz,
+            slab.base, slab.total_bytes, ft, rt);
+        marks.mark(kServeGather);
+        if (timing) t_cat = now_us();
+        // Rows and table stay as they are until this batch's synchronise:
+        // actors rewrite a row only after complete_rows(), the table is
+        // this thread's, and loop() synchronises after a failed batch.
+        launch_gather_rows(ft, rt, b, fsz,
+                           staging.d_frames.data_ptr<uint8_t>(),
+                           staging.d_rew.data_ptr<float>());
+      } else {
+        uint8_t* hf = staging.h_frames.data_ptr<uint8_t>();
+        float* hr = staging.h_rew.data_ptr<float>();
+        for (int64_t r = 0; r < b; ++r) {
+          std::memcpy(hf + r * fsz, reqs[r].leaf_ptr(0), fsz);
+          const float v =
+              *reinterpret_cast<const float*>(reqs[r].leaf_ptr(1));
+          hr[r] = v < -1.f ? -1.f : (v > 1.f ? 1.f : v);
+        }
+        marks.mark(kServeGather);
+        if (timing) t_cat = now_us();  // gather is this path's "cat"
+        hip_check(hipMemcpyAsync(staging.d_frames.data_ptr(), hf, b * fsz,
+                                 hipMemcpyHostToDevice, stream.stream()),
+                  "frame H2D");
+        hip_check(hipMemcpyAsync(staging.d_rew.data_ptr(), hr, b * 4,
+                                 hipMemcpyHostToDevice, stream.stream()),
+                  "reward H2D");
       }
-      marks.mark(kServeGather);
-      if (timing) t_cat = now_us();  // gather is this path's "cat"
-      hip_check(hipMemcpyAsync(staging.d_frames.data_ptr(), hf, b * fsz,
-                               hipMemcpyHostToDevice, stream.stream()),
-                "frame H2D");
-      hip_check(hipMemcpyAsync(staging.d_rew.data_ptr(), hr, b * 4,
-                               hipMemcpyHostToDevice, stream.stream()),
-                "reward H2D");
       frames_p = staging.d_frames.narrow(0, 0, bp);
       rew = staging.d_rew.narrow(0, 0, bp);
     } else if (slot_mode) {
@@ -534,6 +588,7 @@ class InferenceRunner {
         batch.complete_rows();
         marks.mark(kServeFanout);
         batcher_->count_row_batch();
+        if (staging.device_gather) batcher_->count_device_gather_batch();
         batches_.fetch_add(1, std::memory_order_relaxed);
         steps_.fetch_add(b, std::memory_order_relaxed);
         if (timing) record_fused_timing(t_cat - t0, t_sync - t_cat);
@@ -698,6 +753,17 @@ class InferenceRunner {
   const bool legacy_serve_ = [] {
     const char* v = std::getenv("TBAMD_ACTOR_FASTPATH");
     return v != nullptr && std::string(v) == "0";
+  }();
+  // TBAMD_ROW_GATHER=host|device forces either gather for every row batch
+  // (A/B only). Default: what the pool's layout asks for, i.e. the device
+  // gather in obs-slab mode and the host gather otherwise.
+  enum RowGather { kRowGatherAuto, kRowGatherHost, kRowGatherDevice };
+  const RowGather row_gather_ = [] {
+    const char* v = std::getenv("TBAMD_ROW_GATHER");
+    if (v == nullptr || *v == '\0') return kRowGatherAuto;
+    if (std::string(v) == "host") return kRowGatherHost;
+    if (std::string(v) == "device") return kRowGatherDevice;
+    throw std::invalid_argument("TBAMD_ROW_GATHER must be host or device");
   }();
   std::atomic<int64_t> t_cat_us_{0}, t_fwd_us_{0}, t_d2h_us_{0};
   std::atomic<int64_t> timed_batches_{0};

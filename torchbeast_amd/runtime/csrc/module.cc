@@ -266,6 +266,45 @@ PYBIND11_MODULE(_tbruntime, m) {
         py::arg("staging"), py::arg("stride"), py::arg("B"),
         py::arg("columns"));
 
+  // ---- inference-batch gather from rollout rows ----
+  m.def("gather_rows_chunk_bytes", &gather_rows_chunk_bytes);
+  // Test-only: the kernel over byte offsets into a pinned uint8 slab.
+  m.def("gather_rows", &gather_rows, py::arg("slab"),
+        py::arg("frame_offsets"), py::arg("reward_offsets"), py::arg("fsz"),
+        py::arg("cap"), py::arg("chunk_bytes") = 0);
+  // Test-only: build_row_table() over plain addresses (never dereferenced).
+  // Returns (frame pointers, reward pointers, access width).
+  m.def(
+      "build_row_table",
+      [](uint64_t slab_base, int64_t slab_bytes,
+         std::vector<uint64_t> frame_addrs, std::vector<uint64_t> reward_addrs,
+         int64_t fsz) {
+        if (frame_addrs.size() != reward_addrs.size()) {
+          throw std::invalid_argument("one reward address per frame address");
+        }
+        const int64_t b = (int64_t)frame_addrs.size();
+        std::vector<const uint8_t*> ft(std::max<int64_t>(b, 1));
+        std::vector<const float*> rt(std::max<int64_t>(b, 1));
+        const unsigned width = build_row_table(
+            b,
+            [&](int64_t r) {
+              return reinterpret_cast<const uint8_t*>(frame_addrs[r]);
+            },
+            [&](int64_t r) {
+              return reinterpret_cast<const uint8_t*>(reward_addrs[r]);
+            },
+            fsz, reinterpret_cast<const uint8_t*>(slab_base), slab_bytes,
+            ft.data(), rt.data());
+        std::vector<uint64_t> fo(b), ro(b);
+        for (int64_t r = 0; r < b; ++r) {
+          fo[r] = reinterpret_cast<uintptr_t>(ft[r]);
+          ro[r] = reinterpret_cast<uintptr_t>(rt[r]);
+        }
+        return std::make_tuple(fo, ro, width);
+      },
+      py::arg("slab_base"), py::arg("slab_bytes"), py::arg("frame_addrs"),
+      py::arg("reward_addrs"), py::arg("fsz"));
+
   // ---- BatchingQueue ----
   py::class_<BatchingQueue, std::shared_ptr<BatchingQueue>>(m, "BatchingQueue")
       .def(py::init<int64_t, std::optional<int64_t>, std::optional<int64_t>,

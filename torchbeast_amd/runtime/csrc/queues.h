@@ -225,11 +225,10 @@ class PinnedSlabPool {
       slot_bytes_ = (slot_bytes + 4095) & ~int64_t(4095);
       int64_t slots = budget_bytes_ / slot_bytes_;
       if (slots < min_slots_) slots = min_slots_;
+      pinned_ = pinned_memory_wanted();
       slab_ = torch::empty(
           {slots * slot_bytes_},
-          torch::TensorOptions()
-              .dtype(torch::kUInt8)
-              .pinned_memory(pinned_memory_wanted()));
+          torch::TensorOptions().dtype(torch::kUInt8).pinned_memory(pinned_));
       for (int64_t i = slots - 1; i >= 0; --i) free_.push_back(i);
       state_.assign(slots, SlotState::FREE);
       total_slots_ = slots;
@@ -315,6 +314,14 @@ class PinnedSlabPool {
                         total_slots_ * slot_bytes_};
   }
 
+  // Is the slab page-locked, i.e. can the GPU read slot addresses as they
+  // are? False before the first acquire, under TBAMD_NO_PIN and without a
+  // GPU.
+  bool is_pinned() const {
+    std::lock_guard<std::mutex> lk(mu_);
+    return slab_.defined() && pinned_;
+  }
+
   std::map<std::string, double> stats() const {
     std::lock_guard<std::mutex> lk(mu_);
     std::map<std::string, double> out;
@@ -351,6 +358,7 @@ class PinnedSlabPool {
   mutable std::mutex mu_;
   std::condition_variable cv_;
   torch::Tensor slab_;
+  bool pinned_ = false;
   int64_t slot_bytes_ = 0;
   int64_t total_slots_ = 0;
   std::vector<int64_t> free_;
@@ -834,6 +842,10 @@ struct RowLayout {
   size_t n_env = 0;
   int64_t rows = 0;  // T + 1
   int64_t slot_bytes = 0;
+  // Obs-slab mode's row form: the C++ runner gathers frames and rewards on
+  // the GPU straight from the rows (runtime_kernels.hip gather_rows) instead
+  // of copying them through pinned staging on the host.
+  bool device_gather = false;
 
   static RowLeaf describe(const torch::Tensor& t) {
     TORCH_CHECK(t.dim() >= 1 && t.size(0) == 1,
@@ -893,7 +905,9 @@ struct ActorMailbox {
   std::string error;
   std::vector<TensorNest> state;
   std::shared_ptr<const RowLayout> layout;
-  std::shared_ptr<void> keepalive;  // the slab the rows point into
+  // The slab the rows point into: kept alive for requests in flight, and
+  // asked for its bounds by whoever hands row addresses to the GPU.
+  std::shared_ptr<PinnedSlabPool> slab;
 
   int64_t outstanding = 0;  // requests submitted and not yet answered
 
@@ -1274,6 +1288,10 @@ class DynamicBatcher {
   void count_row_batch() {
     row_batches_.fetch_add(1, std::memory_order_relaxed);
   }
+  // Those of them whose frames and rewards the GPU gathered from the rows.
+  void count_device_gather_batch() {
+    device_gather_batches_.fetch_add(1, std::memory_order_relaxed);
+  }
 
   TensorNest compute(TensorNest inputs) {
     const int64_t t0 = now_us();
@@ -1320,6 +1338,8 @@ class DynamicBatcher {
     serve_counters_.report("serve", serve_stage_names(), "batches",
                            "requests", &out);
     out["serve_row_batches"] = (double)row_batches_.load();
+    out["serve_device_gather_batches"] =
+        (double)device_gather_batches_.load();
     out["computes"] = roundtrip_stats_.n.load();
     out["batches"] = batch_size_stats_.n.load();
     if (roundtrip_stats_.n > 0) {
@@ -1345,6 +1365,7 @@ class DynamicBatcher {
     service_stats_.reset();
     serve_counters_.reset();
     row_batches_.store(0, std::memory_order_relaxed);
+    device_gather_batches_.store(0, std::memory_order_relaxed);
   }
 
  private:
@@ -1360,6 +1381,7 @@ class DynamicBatcher {
   mutable StageStats batch_size_stats_;  // sum_us field holds summed sizes
   CpuStageCounters serve_counters_;
   std::atomic<int64_t> row_batches_{0};
+  std::atomic<int64_t> device_gather_batches_{0};
 };
 
 }  // namespace tbruntime

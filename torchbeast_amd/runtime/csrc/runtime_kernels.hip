@@ -16,6 +16,12 @@
 // unpack_rollouts: the learner queue's batch assembly. B rollout slots are
 // DMAed whole into a staging buffer; this kernel transposes them into the
 // [T+1, B, ...] leaves in one launch (rollout_gather.h has the layout).
+//
+// gather_rows: the inference batch of the row form in obs-slab mode (large
+// frames). Requests are rows of the pinned rollout slab; the kernel reads a
+// pinned table of row addresses (row_gather.h) and copies frames and clamped
+// rewards over the host link into the serve thread's device staging, so no
+// frame is copied on the host at all.
 
 #include <ATen/cuda/CUDAContext.h>
 #include <c10/cuda/CUDAGuard.h>
@@ -227,9 +233,177 @@ __global__ __launch_bounds__(kUnpackThreads) void unpack_rollouts_kernel(
   }
 }
 
+// gather_rows: an inference batch gathered straight from rollout rows. The
+// table (pinned host memory, read in place) holds one frame pointer and one
+// reward pointer per request, all inside the pinned rollout slab
+// (row_gather.h checks that on the host). Frame r goes to out_frames row r,
+// reward r is clamped to [-1, 1] into out_rew[r]; rows >= b of both outputs
+// are not touched.
+//
+// Grid (chunks_per_frame, b): a frame is cut into kChunk-byte pieces so that
+// a small batch of large frames still covers the chip (b = 64 frames of
+// 100,800 bytes make 448 workgroups at 16 KB) and no workgroup queues a whole
+// frame's host-link reads behind one another. The two block indices are the
+// chunk and the row: no division anywhere. Lanes stride over the chunk with
+// `width`-byte accesses (16, 8, 4 or 1; uniform per launch, computed on the
+// host over fsz and every source address; kChunk is a multiple of 16 and
+// the destination rows are fsz apart in a 256-byte aligned buffer, so both
+// sides are aligned). Host rows are read once: non-temporal loads. The
+// destination is read next by the trunk: plain stores.
+constexpr int kGatherRowsThreads = 256;
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+
+// Copies n_bytes (a multiple of sizeof(V)) with all lanes of the workgroup.
+// A full chunk has a compile-time trip count, so its loads are all issued
+// before the first store waits on one: kChunk / (256 * 16) host-link reads
+// in flight per lane.
+template <typename V, int kChunk>
+__device__ __forceinline__ void gather_chunk(uint8_t* __restrict__ dst,
+                                             const uint8_t* __restrict__ src,
+                                             int n_bytes) {
+  auto* d = reinterpret_cast<V*>(dst);
+  const auto* s = reinterpret_cast<const V*>(src);
+  constexpr int kPerLane = kChunk / (kGatherRowsThreads * (int)sizeof(V));
+  if constexpr (kPerLane <= 16) {
+    if (n_bytes == kChunk) {
+      V v[kPerLane];
+#pragma unroll
+      for (int k = 0; k < kPerLane; ++k) {
+        v[k] = __builtin_nontemporal_load(s + k * kGatherRowsThreads +
+                                          (int)threadIdx.x);
+      }
+#pragma unroll
+      for (int k = 0; k < kPerLane; ++k) {
+        d[k * kGatherRowsThreads + (int)threadIdx.x] = v[k];
+      }
+      return;
+    }
+  }
+  const int n = n_bytes / (int)sizeof(V);
+  for (int i = (int)threadIdx.x; i < n; i += kGatherRowsThreads) {
+    d[i] = __builtin_nontemporal_load(s + i);
+  }
+}
+
+template <int kChunk>
+__global__ __launch_bounds__(kGatherRowsThreads) void gather_rows_kernel(
+    const uint8_t* const* __restrict__ frame_src,  // host pinned [b]
+    const float* const* __restrict__ rew_src,      // host pinned [b]
+    int fsz, int width,
+    uint8_t* __restrict__ out_frames,  // [cap, fsz]
+    float* __restrict__ out_rew) {     // [cap]
+  static_assert(kChunk % (kGatherRowsThreads * 16) == 0, "chunk granularity");
+  const int r = blockIdx.y;
+  const int begin = (int)blockIdx.x * kChunk;
+  const int n = min(kChunk, fsz - begin);
+  const uint8_t* src = frame_src[r] + begin;
+  uint8_t* dst = out_frames + (int64_t)r * fsz + begin;
+  if (width == 16) {
+    gather_chunk<u32x4, kChunk>(dst, src, n);
+  } else if (width == 8) {
+    gather_chunk<u32x2, kChunk>(dst, src, n);
+  } else if (width == 4) {
+    gather_chunk<uint32_t, kChunk>(dst, src, n);
+  } else {
+    gather_chunk<uint8_t, kChunk>(dst, src, n);
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    const float v = __builtin_nontemporal_load(rew_src[r]);
+    out_rew[r] = v < -1.f ? -1.f : (v > 1.f ? 1.f : v);
+  }
+}
+
 }  // namespace
 
 // Host wrappers -------------------------------------------------------------
+
+int64_t gather_rows_chunk_bytes() { return kGatherRowsChunkBytes; }
+
+void launch_gather_rows(const uint8_t* const* frame_src,
+                        const float* const* rew_src, int64_t b, int64_t fsz,
+                        uint8_t* out_frames, float* out_rew,
+                        int64_t chunk_bytes) {
+  TORCH_CHECK(b >= 1 && fsz >= 1, "gather_rows: empty batch or frame");
+  TORCH_CHECK(frame_src != nullptr && rew_src != nullptr &&
+                  out_frames != nullptr && out_rew != nullptr,
+              "gather_rows: null argument");
+  TORCH_CHECK(fsz < (int64_t(1) << 31), "gather_rows: frame too large");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(out_frames) % 16 == 0,
+              "gather_rows: output frames must be 16-byte aligned");
+  const int64_t chunks = (fsz + chunk_bytes - 1) / chunk_bytes;
+  // gridDim.y carries the row.
+  TORCH_CHECK(b <= 65535 && b * chunks < (int64_t(1) << 31),
+              "gather_rows: grid too big");
+  // The table is pinned host memory: the host reads it as well.
+  uint64_t bits = (uint64_t)fsz;
+  for (int64_t r = 0; r < b; ++r) {
+    bits |= (uint64_t)reinterpret_cast<uintptr_t>(frame_src[r]);
+  }
+  const int width = (int)row_access_width(bits);
+  const dim3 grid((uint32_t)chunks, (uint32_t)b);
+  const dim3 block(kGatherRowsThreads);
+  hipStream_t stream = at::cuda::getCurrentCUDAStream();
+#define TBAMD_GATHER_ROWS(KB)                                                \
+  hipLaunchKernelGGL(gather_rows_kernel<KB * 1024>, grid, block, 0, stream, \
+                     frame_src, rew_src, (int)fsz, width, out_frames, out_rew)
+  switch (chunk_bytes) {
+    case 4096: TBAMD_GATHER_ROWS(4); break;
+    case 8192: TBAMD_GATHER_ROWS(8); break;
+    case 16384: TBAMD_GATHER_ROWS(16); break;
+    case 32768: TBAMD_GATHER_ROWS(32); break;
+    default: TORCH_CHECK(false, "gather_rows: chunk must be 4, 8, 16 or 32 KB");
+  }
+#undef TBAMD_GATHER_ROWS
+  const hipError_t err = hipGetLastError();
+  TORCH_CHECK(err == hipSuccess, "gather_rows launch: ",
+              hipGetErrorString(err));
+}
+
+std::tuple<torch::Tensor, torch::Tensor> gather_rows(
+    torch::Tensor slab, std::vector<int64_t> frame_offsets,
+    std::vector<int64_t> reward_offsets, int64_t fsz, int64_t cap,
+    int64_t chunk_bytes) {
+  TORCH_CHECK(slab.device().is_cpu() && slab.scalar_type() == torch::kUInt8 &&
+                  slab.is_contiguous() && slab.is_pinned(),
+              "gather_rows: slab must be a contiguous pinned uint8 tensor");
+  const int64_t b = (int64_t)frame_offsets.size();
+  TORCH_CHECK(b >= 1 && reward_offsets.size() == frame_offsets.size() &&
+                  cap >= b && fsz >= 1,
+              "gather_rows: need 1 <= b <= cap offsets of each kind");
+  const int64_t total = slab.numel();
+  for (int64_t r = 0; r < b; ++r) {
+    const int64_t f = frame_offsets[r], w = reward_offsets[r];
+    TORCH_CHECK_INDEX(f >= 0 && f <= total && fsz <= total - f,
+                      "gather_rows: frame ", r, " leaves the slab");
+    TORCH_CHECK_INDEX(w >= 0 && w <= total && 4 <= total - w,
+                      "gather_rows: reward ", r, " leaves the slab");
+  }
+  if (chunk_bytes == 0) chunk_bytes = kGatherRowsChunkBytes;
+  auto table = torch::empty({2 * b}, torch::TensorOptions()
+                                         .dtype(torch::kInt64)
+                                         .pinned_memory(true));
+  auto** ft = reinterpret_cast<const uint8_t**>(table.data_ptr<int64_t>());
+  auto** rt = reinterpret_cast<const float**>(table.data_ptr<int64_t>() + b);
+  const uint8_t* base = slab.data_ptr<uint8_t>();
+  // Checks every range once more, against the slab's addresses.
+  build_row_table(
+      b, [&](int64_t r) { return base + frame_offsets[r]; },
+      [&](int64_t r) { return base + reward_offsets[r]; }, fsz, base, total,
+      ft, rt);
+  auto dev = torch::Device(torch::kCUDA, at::cuda::current_device());
+  auto frames = torch::full({cap, fsz}, 0xA5,
+                            torch::TensorOptions().dtype(torch::kUInt8).device(dev));
+  auto rew = torch::full({cap, 1}, -7.0f,
+                         torch::TensorOptions().dtype(torch::kFloat32).device(dev));
+  launch_gather_rows(ft, rt, b, fsz, frames.data_ptr<uint8_t>(),
+                     rew.data_ptr<float>(), chunk_bytes);
+  // The kernel reads `table` and `slab` in place: neither may go away or
+  // change under it.
+  at::cuda::getCurrentCUDAStream().synchronize();
+  return {frames, rew};
+}
 
 void launch_unpack_rollouts(const uint8_t* staging, int64_t stride, int64_t B,
                             const UnpackColumn* columns, int n_columns) {
