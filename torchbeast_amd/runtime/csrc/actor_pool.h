@@ -93,8 +93,7 @@ class ActorPool {
       learner_queue_->set_source_pool(rollout_pool_);
     }
     // TBAMD_ACTOR_FASTPATH=0 keeps the nest/promise loops below (A/B only).
-    const char* fp = std::getenv("TBAMD_ACTOR_FASTPATH");
-    const bool fastpath = !(fp != nullptr && std::string(fp) == "0");
+    const bool fastpath = actor_fastpath_enabled();
     // Obs-slab mode has a row form for stateless agents: the frame is
     // written once, into its rollout row, and the runner gathers the batch
     // from the rows on the GPU (RowLayout::device_gather). No second slab,

@@ -3,14 +3,23 @@
 // The reference serves inference from Python threads
 // (ref: polybeast_learner.py:269-285); at MI355X throughput that path is
 // GIL-bound (measured ~20-45 ms service latency for ~0.3 ms of GPU work).
-// This runner consumes DynamicBatcher batches entirely in C++:
-//   get_batch -> pinned-host cat -> H2D on a dedicated HIP stream ->
-//   AtariNet forward (ATen ops; custom fused kernels swap in at the op
-//   level) -> sampled action -> D2H -> set_outputs.
-// Row batches (requests that are rows of rollout slots) skip the cat: their
-// frames are gathered into persistent staging either on the host (one
-// memcpy per frame, then one H2D) or, in obs-slab mode, by gather_rows_kernel
-// reading the rows over the host link.
+// This runner consumes DynamicBatcher batches entirely in C++, each serve
+// thread on a HIP stream of its own. serve() is a pipeline of stages that
+// hand a ServeInputs along:
+//   input   a device batch padded to 64, from one of three request forms:
+//           rows of rollout slots, gathered into persistent staging on the
+//           host (one memcpy per frame, one H2D) or, in obs-slab mode, by
+//           gather_rows_kernel over the host link (inputs_from_rows); actor
+//           ids into the pinned obs slab, gathered by gather_obs
+//           (inputs_from_slots); tensors, cat-ed on the host by the batcher,
+//           then H2D (inputs_from_tensors).
+//   trunk   frames -> conv features -> fc: hand-written MFMA or fused conv
+//           kernels, ATen/MIOpen for the rest. bf16 weight packs are cached
+//           until mark_weights_dirty().
+//   tail    heads, the batch's one stream synchronise, delivery: fused heads
+//           scattered into the rows (tail_fused_rows) or into pinned tensors
+//           (tail_fused), or LSTM core + ATen heads + D2H (tail_generic).
+//   finish  counters, warmed batch sizes, TBAMD_SERVE_TIMINGS.
 // Behavior-model weights are VIEWS of the learner's flat actor buffer, so
 // weight sync stays one flat device copy with no runner involvement.
 
@@ -22,7 +31,6 @@
 #include <torch/extension.h>
 
 #include <atomic>
-#include <chrono>
 #include <cstdlib>
 #include <mutex>
 #include <set>
@@ -61,6 +69,16 @@ class InferenceRunner {
                 "runner weight list too short for model/lstm config");
     TORCH_CHECK(weights_[0].is_cuda(), "runner weights must be on the GPU");
     device_ = weights_[0].device();
+    // Deep 84x84 trunk serves on the hand-written MFMA 3x3 kernels
+    // (conv_mfma.hip resnet_conv); MIOpen only for other geometries.
+    deep_mfma_ = deep_ && !aten_only_ && weights_[0].size(0) == 16 &&
+                 weights_[0].size(1) <= 8 && weights_[0].size(2) == 3 &&
+                 tbamd::resnet_conv_supported(16, 42, 16);
+    // The fused heads take a stateless core of [fc output, reward].
+    fused_heads_ = !aten_only_ && num_lstm_layers_ == 0 &&
+                   weights_[head_base_].size(0) <= 64 &&
+                   weights_[head_base_].size(1) ==
+                       weights_[head_base_ - 2].size(0) + 1;
   }
 
   ~InferenceRunner() { stop(); }
@@ -115,6 +133,7 @@ class InferenceRunner {
     torch::NoGradGuard no_grad;
     RowStaging staging;
     CpuMarks marks;
+    marks.timing = serve_timing_;
     CpuStageCounters& cnt = batcher_->serve_counters();
 
     while (running_) {
@@ -150,11 +169,15 @@ class InferenceRunner {
     }
   }
 
-  // Per-batch CPU-time sampling for one serve thread: mark(stage) charges
-  // the CPU time since the previous sample to `stage`.
+  // Per-batch time sampling for one serve thread. mark(stage) charges the
+  // CPU time since the previous sample to `stage`. Under TBAMD_SERVE_TIMINGS
+  // stamp() also takes the batch's wall-clock stage boundaries (microseconds):
+  // start, inputs on the host ("cat"), forward enqueued, outputs on the host.
   struct CpuMarks {
     int64_t last = 0;
     int64_t ns[CpuStageCounters::kStages];
+    bool timing = false;
+    int64_t t0 = 0, t_cat = 0, t_fwd = 0, t_sync = 0;
     void begin() {
       for (auto& v : ns) v = 0;
       last = thread_cpu_ns();
@@ -163,6 +186,9 @@ class InferenceRunner {
       const int64_t now = thread_cpu_ns();
       ns[stage] += now - last;
       last = now;
+    }
+    void stamp(int64_t& t) {
+      if (timing) t = now_us();
     }
   };
 
@@ -182,6 +208,22 @@ class InferenceRunner {
     torch::Tensor h_action, h_logits, h_base;        // pinned outputs
   };
 
+  // What the input stage hands to the trunk and the tail.
+  struct ServeInputs {
+    int64_t b = 0, bp = 0, C = 0, H = 0, W = 0;
+    torch::Tensor frames;   // [bp, C, H, W] u8, device; rows >= b hold some
+                            // valid u8 frame
+    torch::Tensor rew;      // [bp, 1] f32, clamped to [-1, 1]
+    torch::Tensor notdone;  // f32, at least b long; undefined for row batches
+    std::vector<torch::Tensor> state;  // [] or h, c [L, b, H]
+    TensorNest source;  // the batcher's nest the copies above read from
+    bool rows = false;  // outputs go back through RowStaging into the rows
+  };
+
+  // Compute batches are multiples of 64 so kernel/solution caches see a
+  // handful of shapes, not every ragged batch size.
+  static int64_t pad64(int64_t n) { return (n + 63) / 64 * 64; }
+
   void ensure_staging(RowStaging& st, int64_t bp,
                       const std::vector<int64_t>& chw, int64_t A,
                       bool device_gather) {
@@ -193,7 +235,7 @@ class InferenceRunner {
     }
     const int64_t want = batcher_->max_batch_size();
     int64_t cap = bp;
-    if (want <= 8192) cap = std::max(cap, (want + 63) / 64 * 64);
+    if (want <= 8192) cap = std::max(cap, pad64(want));
     auto hopts = torch::TensorOptions().pinned_memory(true);
     auto dopts = torch::TensorOptions().device(device_);
     if (device_gather) {
@@ -206,7 +248,8 @@ class InferenceRunner {
       st.h_table = torch::Tensor();
     }
     st.device_gather = device_gather;
-    // Zero once: pad rows (>= b) are never written again, see serve_rows.
+    // Zero once: pad rows (>= b) are never written again, see
+    // inputs_from_rows.
     st.d_frames = torch::zeros({cap, chw[0], chw[1], chw[2]},
                                dopts.dtype(torch::kUInt8));
     st.d_rew = torch::zeros({cap, 1}, dopts.dtype(torch::kFloat32));
@@ -221,51 +264,18 @@ class InferenceRunner {
   // Can this batch take the allocation-free row path? Stateless model with
   // the fused heads, every request a row of the flagship step layout.
   bool rows_servable(const DynamicBatcher::Batch& batch) const {
-    if (!batch.all_rows() || num_lstm_layers_ != 0 || aten_only_ ||
-        legacy_serve_) {
-      return false;
-    }
+    if (!batch.all_rows() || !fused_heads_ || legacy_serve_) return false;
     const auto& req = batch.requests()[0];
-    const RowLayout& l = *req.layout;
-    if (!req.state().empty()) return false;
-    if (l.n_env < 3 || l.leaves.size() != l.n_env + 3) return false;
-    const auto& f = l.leaves[0];
-    const int64_t A = weights_[head_base_].size(0);
-    const auto& lv = l.leaves;
-    // The fused heads take [fc output, reward].
-    if (weights_[head_base_].size(1) != weights_[head_base_ - 2].size(0) + 1) {
-      return false;
-    }
-    return f.dtype == torch::kUInt8 && f.shape.size() == 5 &&
-           lv[1].dtype == torch::kFloat32 && lv[1].row_bytes == 4 &&
-           lv[l.n_env].dtype == torch::kInt64 && lv[l.n_env].row_bytes == 8 &&
-           lv[l.n_env + 1].dtype == torch::kFloat32 &&
-           lv[l.n_env + 1].row_bytes == 4 * A &&
-           lv[l.n_env + 2].dtype == torch::kFloat32 &&
-           lv[l.n_env + 2].row_bytes == 4 && A <= 64;
+    return req.state().empty() &&
+           req.layout->is_flagship_step(weights_[head_base_].size(0));
   }
 
   static void hip_check(hipError_t e, const char* what) {
     TORCH_CHECK(e == hipSuccess, what, ": ", hipGetErrorString(e));
   }
 
-  // TBAMD_SERVE_TIMINGS bookkeeping of the fused-heads paths (tensor and
-  // row): cat/gather, then forward + synchronise.
-  void record_fused_timing(int64_t cat_us, int64_t fwd_us) {
-    t_cat_us_.fetch_add(cat_us, std::memory_order_relaxed);
-    t_fwd_us_.fetch_add(fwd_us, std::memory_order_relaxed);
-    const int64_t n = timed_batches_.fetch_add(1) + 1;
-    if (n % 500 == 0) {
-      fprintf(stderr,
-              "[serve timings over %lld batches] cat=%.0fus "
-              "fwd+sync=%.0fus\n",
-              (long long)n, (double)t_cat_us_.load() / n,
-              (double)t_fwd_us_.load() / n);
-    }
-  }
-
   void trace(const char* what) {
-    if (std::getenv("TBAMD_SERVE_TRACE")) {
+    if (trace_) {
       fprintf(stderr, "[serve %p] %s\n", (void*)this, what);
       fflush(stderr);
     }
@@ -274,223 +284,224 @@ class InferenceRunner {
   void serve(DynamicBatcher::Batch& batch, at::cuda::CUDAStream& stream,
              RowStaging& staging, CpuMarks& marks) {
     trace("begin");
-    const bool rows = rows_servable(batch);
-    // Stage timers (enabled by TBAMD_SERVE_TIMINGS): cat / fwd / d2h+sync.
-    const bool timing = serve_timing_;
-    auto now_us = []() {
-      return std::chrono::duration_cast<std::chrono::microseconds>(
-                 std::chrono::steady_clock::now().time_since_epoch())
-          .count();
-    };
-    int64_t t0 = timing ? now_us() : 0;
-    TensorNest inputs;
-    if (!rows) inputs = batch.get_inputs();
+    marks.stamp(marks.t0);
+    ServeInputs in;
+    if (rows_servable(batch)) {
+      in = inputs_from_rows(batch, stream, staging, marks);
+    } else {
+      // nest = ((frame, reward, done, ...), state)  [classic requests]
+      //      = (slot_ids, state)                     [obs-slab requests]
+      TensorNest nest = batch.get_inputs();
+      marks.stamp(marks.t_cat);
+      in = nest.vector()[0].is_leaf() ? inputs_from_slots(nest)
+                                      : inputs_from_tensors(nest);
+      in.source = std::move(nest);
+      marks.mark(kServeGather);
+    }
     trace("cat-done");
-    int64_t t_cat = timing ? now_us() : 0;
-    // Serialize the FIRST forward of each quantized batch size: concurrent
-    // MIOpen solution-finds for a brand-new conv shape across streams have
-    // been observed to fault; once found, the solution cache makes later
-    // serves safe to run fully in parallel.
-    const int64_t bq = (batch.size() + 63) / 64 * 64;
-    // Deep 84x84 trunk serves on the hand-written MFMA 3x3 kernels
-    // (conv_mfma.hip resnet_conv); MIOpen only for other geometries.
-    const bool deep_mfma =
-        deep_ && !aten_only_ && weights_[0].size(0) == 16 &&
-        weights_[0].size(1) <= 8 && weights_[0].size(2) == 3 &&
-        tbamd::resnet_conv_supported(16, 42, 16);
+    // Only the MIOpen (deep ResNet) path needs first-serve-per-shape
+    // serialization: concurrent solution-finds for a brand-new conv shape
+    // across streams have been observed to fault; once found, the solution
+    // cache makes later serves safe to run fully in parallel. The
+    // hand-written trunk kernels have no such state. Held until the outputs
+    // are delivered; the size counts as warmed only if that succeeds.
+    const int64_t bq = pad64(batch.size());
     std::unique_lock<std::mutex> warm_lock;
-    if (deep_ && !deep_mfma) {
-      // Only the MIOpen (deep ResNet) path needs first-serve-per-shape
-      // serialization: concurrent solution-finds for a new conv shape
-      // across streams have been observed to fault. The hand-written
-      // trunk kernels have no such state.
+    if (deep_ && !deep_mfma_) {
       bool is_new;
       {
         std::lock_guard<std::mutex> g(warm_mu_);
         is_new = warmed_sizes_.count(bq) == 0;
       }
-      if (is_new) {
-        warm_lock = std::unique_lock<std::mutex>(serve_mu_);
-      }
+      if (is_new) warm_lock = std::unique_lock<std::mutex>(serve_mu_);
     }
-    // inputs = ((frame, reward, done, ...), state)  [classic requests]
-    //        = (slot_ids, state)                     [obs-slab requests]
-    const bool slot_mode = !rows && inputs.vector()[0].is_leaf();
-    std::vector<torch::Tensor> state;  // [] or h,c [L,b,H]
-    if (!rows) state = inputs.vector()[1].flatten();
-    auto opts = torch::TensorOptions().device(device_);
-
-    int64_t b, bp, C, H, W;
-    torch::Tensor frames_p, rew, nd_gpu;
-    if (rows) {
-      // Row batch: gather each request's frame into the pinned staging (the
-      // one host copy before DMA), clamp rewards on the host while at it,
-      // then one H2D for frames and one for rewards. No tensor is
-      // allocated and no clamp / not / cast / fill kernel runs.
-      //
-      // Pad rows [b, bp) are NOT zeroed. The trunk convolves each sample
-      // on its own, fc is a row-wise GEMM and the heads kernel launches
-      // exactly b workgroups, so no row >= b ever reaches an output; and
-      // whatever a pad row holds (the zeros it was allocated with, or an
-      // older batch's frame) is a valid u8 frame, so nothing non-finite can
-      // arise from it either. The same holds for the device gather below:
-      // its kernel writes rows [0, b) of d_frames / d_rew and nothing else.
-      const auto& reqs = batch.requests();
-      const RowLayout& l = *reqs[0].layout;
-      b = (int64_t)reqs.size();
-      bp = (b + 63) / 64 * 64;
-      C = l.leaves[0].shape[2];
-      H = l.leaves[0].shape[3];
-      W = l.leaves[0].shape[4];
-      // Device gather: the GPU reads each frame and reward from its row in
-      // the pinned rollout slab (large frames, where the host copy below is
-      // what bounds the serve thread). Needs host addresses the GPU can
-      // read, i.e. a pinned slab.
-      const auto& pool = reqs[0].mailbox->slab;
-      const bool device_gather =
-          (row_gather_ == kRowGatherAuto ? l.device_gather
-                                         : row_gather_ == kRowGatherDevice) &&
-          pool != nullptr && pool->is_pinned();
-      ensure_staging(staging, bp, {C, H, W}, weights_[head_base_].size(0),
-                     device_gather);
-      const int64_t fsz = staging.fsz;
-      if (device_gather) {
-        // One layout per batch means one pool per batch. The table is
-        // written only here, and only with addresses checked against the
-        // slab: a stray one would be a GPU fault.
-        const SlabGeometry slab = pool->geometry();
-        int64_t* table = staging.h_table.data_ptr<int64_t>();
-        auto** ft = reinterpret_cast<const uint8_t**>(table);
-        auto** rt = reinterpret_cast<const float**>(table + staging.cap);
-        build_row_table(
-            b, [&reqs](int64_t r) { return reqs[r].leaf_ptr(0); },
-            [&reqs](int64_t r) { return reqs[r].leaf_ptr(1); }, fsz,
-            slab.base, slab.total_bytes, ft, rt);
-        marks.mark(kServeGather);
-        if (timing) t_cat = now_us();
-        // Rows and table stay as they are until this batch's synchronise:
-        // actors rewrite a row only after complete_rows(), the table is
-        // this thread's, and loop() synchronises after a failed batch.
-        launch_gather_rows(ft, rt, b, fsz,
-                           staging.d_frames.data_ptr<uint8_t>(),
-                           staging.d_rew.data_ptr<float>());
-      } else {
-        uint8_t* hf = staging.h_frames.data_ptr<uint8_t>();
-        float* hr = staging.h_rew.data_ptr<float>();
-        for (int64_t r = 0; r < b; ++r) {
-          std::memcpy(hf + r * fsz, reqs[r].leaf_ptr(0), fsz);
-          const float v =
-              *reinterpret_cast<const float*>(reqs[r].leaf_ptr(1));
-          hr[r] = v < -1.f ? -1.f : (v > 1.f ? 1.f : v);
-        }
-        marks.mark(kServeGather);
-        if (timing) t_cat = now_us();  // gather is this path's "cat"
-        hip_check(hipMemcpyAsync(staging.d_frames.data_ptr(), hf, b * fsz,
-                                 hipMemcpyHostToDevice, stream.stream()),
-                  "frame H2D");
-        hip_check(hipMemcpyAsync(staging.d_rew.data_ptr(), hr, b * 4,
-                                 hipMemcpyHostToDevice, stream.stream()),
-                  "reward H2D");
-      }
-      frames_p = staging.d_frames.narrow(0, 0, bp);
-      rew = staging.d_rew.narrow(0, 0, bp);
-    } else if (slot_mode) {
-      const auto& top = inputs.vector();
-      TORCH_CHECK(has_slab_, "slot-id request but no obs slab configured");
-      const torch::Tensor ids = top[0].leaf();  // [1, b] int32
-      b = ids.size(1);
-      bp = (b + 63) / 64 * 64;
-      auto g = gather_obs(slab_frames_, slab_rew_, slab_done_, ids, bp,
-                          frame_shape_);
-      frames_p = g[0];
-      rew = g[1];
-      nd_gpu = g[2];
-      C = frame_shape_[0];
-      H = frame_shape_[1];
-      W = frame_shape_[2];
+    torch::Tensor x = trunk(in, stream);
+    if (!fused_heads_) {
+      tail_generic(batch, in, x, stream, marks);
+    } else if (in.rows) {
+      tail_fused_rows(batch, in, x, stream, staging, marks);
     } else {
-      const auto& env = inputs.vector()[0].vector();
-      const torch::Tensor frame = env[0].leaf();   // [1, b, C, H, W] u8
-      const torch::Tensor reward = env[1].leaf();  // [1, b] f32
-      const torch::Tensor done = env[2].leaf();    // [1, b] bool
-      b = frame.size(1);
-      // Quantize the compute batch to multiples of 64 so kernel/solution
-      // caches see a handful of shapes, not every ragged batch size.
-      bp = (b + 63) / 64 * 64;
-      C = frame.size(2);
-      H = frame.size(3);
-      W = frame.size(4);
-      frames_p = torch::empty({bp, C, H, W}, opts.dtype(torch::kUInt8));
-      frames_p.narrow(0, 0, b).copy_(frame.reshape({b, C, H, W}),
-                                     /*non_blocking=*/true);
-      if (bp > b) frames_p.narrow(0, b, bp - b).zero_();
-      rew = torch::empty({bp, 1}, opts.dtype(torch::kFloat32));
-      rew.narrow(0, 0, b)
-          .copy_(reward.to(opts.dtype(torch::kFloat32), true).reshape({b, 1}))
-          .clamp_(-1, 1);
-      if (bp > b) rew.narrow(0, b, bp - b).zero_();
-      nd_gpu = (~done.reshape({b}))
-                   .to(opts.dtype(torch::kFloat32), /*non_blocking=*/true);
+      tail_fused(batch, in, x, stream, marks);
     }
-    if (!rows) marks.mark(kServeGather);
+    finish(in, staging, marks, warm_lock.owns_lock() ? bq : 0);
+  }
 
+  // ---- input stage ----
+  // Row batch: gather each request's frame into the pinned staging (the
+  // one host copy before DMA), clamp rewards on the host while at it,
+  // then one H2D for frames and one for rewards. No tensor is
+  // allocated and no clamp / not / cast / fill kernel runs.
+  //
+  // Pad rows [b, bp) are NOT zeroed. The trunk convolves each sample
+  // on its own, fc is a row-wise GEMM and the heads kernel launches
+  // exactly b workgroups, so no row >= b ever reaches an output; and
+  // whatever a pad row holds (the zeros it was allocated with, or an
+  // older batch's frame) is a valid u8 frame, so nothing non-finite can
+  // arise from it either. The same holds for the device gather:
+  // its kernel writes rows [0, b) of d_frames / d_rew and nothing else.
+  ServeInputs inputs_from_rows(DynamicBatcher::Batch& batch,
+                               at::cuda::CUDAStream& stream,
+                               RowStaging& staging, CpuMarks& marks) {
+    const auto& reqs = batch.requests();
+    const RowLayout& l = *reqs[0].layout;
+    ServeInputs in;
+    in.rows = true;
+    in.b = (int64_t)reqs.size();
+    in.bp = pad64(in.b);
+    in.C = l.leaves[0].shape[2];
+    in.H = l.leaves[0].shape[3];
+    in.W = l.leaves[0].shape[4];
+    const int64_t b = in.b;
+    // Device gather: the GPU reads each frame and reward from its row in
+    // the pinned rollout slab (large frames, where the host copy below is
+    // what bounds the serve thread). Needs host addresses the GPU can
+    // read, i.e. a pinned slab.
+    const auto& pool = reqs[0].mailbox->slab;
+    const bool device_gather =
+        (row_gather_ == kRowGatherAuto ? l.device_gather
+                                       : row_gather_ == kRowGatherDevice) &&
+        pool != nullptr && pool->is_pinned();
+    ensure_staging(staging, in.bp, {in.C, in.H, in.W},
+                   weights_[head_base_].size(0), device_gather);
+    const int64_t fsz = staging.fsz;
+    if (device_gather) {
+      // One layout per batch means one pool per batch. The table is
+      // written only here, and only with addresses checked against the
+      // slab: a stray one would be a GPU fault.
+      const SlabGeometry slab = pool->geometry();
+      int64_t* table = staging.h_table.data_ptr<int64_t>();
+      auto** ft = reinterpret_cast<const uint8_t**>(table);
+      auto** rt = reinterpret_cast<const float**>(table + staging.cap);
+      build_row_table(
+          b, [&reqs](int64_t r) { return reqs[r].leaf_ptr(0); },
+          [&reqs](int64_t r) { return reqs[r].leaf_ptr(1); }, fsz, slab.base,
+          slab.total_bytes, ft, rt);
+      marks.mark(kServeGather);
+      marks.stamp(marks.t_cat);
+      // Rows and table stay as they are until this batch's synchronise:
+      // actors rewrite a row only after complete_rows(), the table is
+      // this thread's, and loop() synchronises after a failed batch.
+      launch_gather_rows(ft, rt, b, fsz, staging.d_frames.data_ptr<uint8_t>(),
+                         staging.d_rew.data_ptr<float>());
+    } else {
+      uint8_t* hf = staging.h_frames.data_ptr<uint8_t>();
+      float* hr = staging.h_rew.data_ptr<float>();
+      for (int64_t r = 0; r < b; ++r) {
+        std::memcpy(hf + r * fsz, reqs[r].leaf_ptr(0), fsz);
+        const float v = *reinterpret_cast<const float*>(reqs[r].leaf_ptr(1));
+        hr[r] = v < -1.f ? -1.f : (v > 1.f ? 1.f : v);
+      }
+      marks.mark(kServeGather);
+      marks.stamp(marks.t_cat);  // gather is this path's "cat"
+      hip_check(hipMemcpyAsync(staging.d_frames.data_ptr(), hf, b * fsz,
+                               hipMemcpyHostToDevice, stream.stream()),
+                "frame H2D");
+      hip_check(hipMemcpyAsync(staging.d_rew.data_ptr(), hr, b * 4,
+                               hipMemcpyHostToDevice, stream.stream()),
+                "reward H2D");
+    }
+    in.frames = staging.d_frames.narrow(0, 0, in.bp);
+    in.rew = staging.d_rew.narrow(0, 0, in.bp);
+    return in;
+  }
+
+  // Slot-id requests: gather_obs reads frames, rewards and dones of the
+  // named actors from the pinned obs slab and zeroes the pad rows.
+  ServeInputs inputs_from_slots(const TensorNest& nest) {
+    TORCH_CHECK(has_slab_, "slot-id request but no obs slab configured");
+    const torch::Tensor ids = nest.vector()[0].leaf();  // [1, b] int32
+    ServeInputs in;
+    in.b = ids.size(1);
+    in.bp = pad64(in.b);
+    in.C = frame_shape_[0];
+    in.H = frame_shape_[1];
+    in.W = frame_shape_[2];
+    auto g = gather_obs(slab_frames_, slab_rew_, slab_done_, ids, in.bp,
+                        frame_shape_);
+    in.frames = g[0];
+    in.rew = g[1];
+    in.notdone = g[2];
+    in.state = nest.vector()[1].flatten();
+    return in;
+  }
+
+  // Tensor requests, already cat-ed on the host by the batcher: H2D into a
+  // fresh padded batch, pad rows zeroed.
+  ServeInputs inputs_from_tensors(const TensorNest& nest) {
+    const auto& env = nest.vector()[0].vector();
+    const torch::Tensor frame = env[0].leaf();   // [1, b, C, H, W] u8
+    const torch::Tensor reward = env[1].leaf();  // [1, b] f32
+    const torch::Tensor done = env[2].leaf();    // [1, b] bool
+    auto opts = torch::TensorOptions().device(device_);
+    ServeInputs in;
+    const int64_t b = in.b = frame.size(1);
+    const int64_t bp = in.bp = pad64(b);
+    in.C = frame.size(2);
+    in.H = frame.size(3);
+    in.W = frame.size(4);
+    in.frames = torch::empty({bp, in.C, in.H, in.W}, opts.dtype(torch::kUInt8));
+    in.frames.narrow(0, 0, b).copy_(frame.reshape({b, in.C, in.H, in.W}),
+                                    /*non_blocking=*/true);
+    if (bp > b) in.frames.narrow(0, b, bp - b).zero_();
+    in.rew = torch::empty({bp, 1}, opts.dtype(torch::kFloat32));
+    in.rew.narrow(0, 0, b)
+        .copy_(reward.to(opts.dtype(torch::kFloat32), true).reshape({b, 1}))
+        .clamp_(-1, 1);
+    if (bp > b) in.rew.narrow(0, b, bp - b).zero_();
+    in.notdone = (~done.reshape({b}))
+                     .to(opts.dtype(torch::kFloat32), /*non_blocking=*/true);
+    in.state = nest.vector()[1].flatten();
+    return in;
+  }
+
+  // ---- trunk ----
+  // bf16-packed trunk weights (3 tensors shallow, 15 deep), cached until the
+  // learner's next sync (mark_weights_dirty). The packing thread
+  // synchronizes its stream before publishing so other serve streams read
+  // complete data.
+  std::vector<torch::Tensor> packed_weights(at::cuda::CUDAStream& stream) {
+    std::lock_guard<std::mutex> g(pack_mu_);
+    const int64_t v = weights_version_.load();
+    if (packed_version_ != v) {
+      packed_ = deep_ ? pack_deep() : pack_shallow();
+      stream.synchronize();
+      packed_version_ = v;
+    }
+    return packed_;
+  }
+
+  std::vector<torch::Tensor> pack_shallow() const {
+    return {weights_[0].reshape({32, -1}).to(torch::kBFloat16).contiguous(),
+            weights_[2].permute({0, 2, 3, 1}).reshape({64, -1})
+                .to(torch::kBFloat16).contiguous(),
+            weights_[4].permute({0, 2, 3, 1}).reshape({64, -1})
+                .to(torch::kBFloat16).contiguous()};
+  }
+
+  std::vector<torch::Tensor> pack_deep() const {
+    std::vector<torch::Tensor> packed;
+    for (size_t wi = 0; wi < 30; wi += 2) {
+      torch::Tensor w = weights_[wi];
+      if (wi == 0 && w.size(1) < 8) {  // first conv: pad channels
+        w = torch::cat({w, w.new_zeros({w.size(0), 8 - w.size(1), 3, 3})}, 1);
+      }
+      auto f = w.permute({0, 2, 3, 1}).reshape({w.size(0), -1})
+                   .to(torch::kBFloat16);
+      const int64_t k = f.size(1), kpad = (k + 31) / 32 * 32 - k;
+      if (kpad) f = torch::cat({f, f.new_zeros({f.size(0), kpad})}, 1);
+      packed.push_back(f.contiguous());
+    }
+    return packed;
+  }
+
+  // Frames to features to fc: [bp, fc width], post-relu.
+  torch::Tensor trunk(const ServeInputs& in, at::cuda::CUDAStream& stream) {
+    const int64_t bp = in.bp, C = in.C, H = in.H, W = in.W;
     torch::Tensor x;
-    if (deep_ && deep_mfma && H == 84 && W == 84 && C <= 8) {
-      // bf16 channels_last trunk, every conv on the MFMA template. Packed
-      // bf16 weights cached until the learner's next sync.
-      std::vector<torch::Tensor> wp;
-      {
-        std::lock_guard<std::mutex> g(pack_mu_);
-        const int64_t v = weights_version_.load();
-        if (deep_packed_version_ != v) {
-          deep_packed_.clear();
-          for (size_t wi = 0; wi < 30; wi += 2) {
-            torch::Tensor w = weights_[wi];
-            if (wi == 0 && w.size(1) < 8) {  // first conv: pad channels
-              w = torch::cat(
-                  {w, w.new_zeros({w.size(0), 8 - w.size(1), 3, 3})}, 1);
-            }
-            auto f = w.permute({0, 2, 3, 1}).reshape({w.size(0), -1})
-                         .to(torch::kBFloat16);
-            const int64_t k = f.size(1), kpad = (k + 31) / 32 * 32 - k;
-            if (kpad) f = torch::cat({f, f.new_zeros({f.size(0), kpad})}, 1);
-            deep_packed_.push_back(f.contiguous());
-          }
-          stream.synchronize();
-          deep_packed_version_ = v;
-        }
-        wp = deep_packed_;
-      }
-      auto x8 = torch::empty({bp, 8, 84, 84}, opts.dtype(torch::kBFloat16),
-                             torch::MemoryFormat::ChannelsLast);
-      x8.zero_();
-      x8.narrow(1, 0, C).copy_(frames_p, /*non_blocking=*/true);
-      x8.mul_(1.0f / 255.0f);
-      size_t wi = 0, pi = 0;
-      auto conv = [&](torch::Tensor t, int64_t ci, int64_t hw, int64_t co) {
-        auto o = tbamd::resnet_conv(t, wp[pi], weights_[wi + 1], ci, hw, co,
-                                    /*fwd=*/true);
-        ++pi;
-        wi += 2;
-        return o.permute({0, 3, 1, 2});
-      };
-      const int64_t widths[3] = {16, 32, 32};
-      int64_t hw = 84, ci = 8;
-      torch::Tensor t = x8;
-      for (int sec = 0; sec < 3; ++sec) {
-        t = conv(t, ci, hw, widths[sec]);
-        t = at::max_pool2d(t, 3, 2, 1);
-        hw = (hw + 1) / 2;
-        ci = widths[sec];
-        for (int res = 0; res < 2; ++res) {
-          torch::Tensor y = conv(at::relu(t), ci, hw, ci);
-          y = conv(at::relu(y), ci, hw, ci);
-          t = t + y;
-        }
-      }
-      x = at::relu(t).to(torch::kFloat32).reshape({bp, -1});
+    if (deep_ && deep_mfma_ && H == 84 && W == 84 && C <= 8) {
+      x = trunk_deep_mfma(in, packed_weights(stream));
     } else if (deep_) {
-      x = frames_p.to(torch::kFloat32).mul_(1.0f / 255.0f);
+      x = in.frames.to(torch::kFloat32).mul_(1.0f / 255.0f);
       size_t wi = 0;
       for (int sec = 0; sec < 3; ++sec) {
         x = at::conv2d(x, weights_[wi], weights_[wi + 1], 1, 1);
@@ -512,136 +523,157 @@ class InferenceRunner {
       // fused kernel whose grid is the batch (underfills the 256 CUs below
       // ~512 samples and was measured dominating GPU time at small
       // batches: profiles/PROFILE_r2.md).
-      torch::Tensor w1p, w2p, w3p;
-      {
-        // bf16-packed trunk weights, cached until the learner's next sync
-        // (mark_weights_dirty). The packing thread synchronizes its stream
-        // before publishing so other serve streams read complete data.
-        std::lock_guard<std::mutex> g(pack_mu_);
-        const int64_t v = weights_version_.load();
-        if (packed_version_ != v) {
-          w1p_ = weights_[0].reshape({32, -1}).to(torch::kBFloat16)
-                     .contiguous();
-          w2p_ = weights_[2].permute({0, 2, 3, 1}).reshape({64, -1})
-                     .to(torch::kBFloat16).contiguous();
-          w3p_ = weights_[4].permute({0, 2, 3, 1}).reshape({64, -1})
-                     .to(torch::kBFloat16).contiguous();
-          stream.synchronize();
-          packed_version_ = v;
-        }
-        w1p = w1p_;
-        w2p = w2p_;
-        w3p = w3p_;
-      }
+      const std::vector<torch::Tensor> wp = packed_weights(stream);
       trace("trunk");
-      x = tbamd::conv_trunk_fwd(frames_p, w1p, weights_[1], w2p, weights_[3],
-                                w3p, weights_[5], /*want_stash=*/false)[0];
+      x = tbamd::conv_trunk_fwd(in.frames, wp[0], weights_[1], wp[1],
+                                weights_[3], wp[2], weights_[5],
+                                /*want_stash=*/false)[0];
       trace("trunk-done");
     } else if (!aten_only_ && bp <= 384 &&
                tbamd::atari_trunk_supported(C, H, W)) {
       // Hand-written fused CDNA4 conv trunk: one kernel for the u8
       // normalize + 3 convs (non-84x84 geometries).
-      x = tbamd::atari_trunk_fwd(frames_p, weights_[0], weights_[1],
+      x = tbamd::atari_trunk_fwd(in.frames, weights_[0], weights_[1],
                                  weights_[2], weights_[3], weights_[4],
                                  weights_[5], /*save_for_backward=*/false)[0];
     } else {
-      x = frames_p.to(torch::kFloat32).mul_(1.0f / 255.0f);
+      x = in.frames.to(torch::kFloat32).mul_(1.0f / 255.0f);
       x = at::conv2d(x, weights_[0], weights_[1], /*stride=*/4).relu_();
       x = at::conv2d(x, weights_[2], weights_[3], 2).relu_();
       x = at::conv2d(x, weights_[4], weights_[5], 1).relu_();
       x = x.reshape({bp, -1});
     }
-    x = at::linear(x, weights_[head_base_ - 2], weights_[head_base_ - 1])
-            .relu_();
+    return at::linear(x, weights_[head_base_ - 2], weights_[head_base_ - 1])
+        .relu_();
+  }
 
-    if (!aten_only_ && num_lstm_layers_ == 0 &&
-        weights_[head_base_].size(0) <= 64 &&
-        weights_[head_base_].size(1) == x.size(1) + 1) {
-      // Fused heads + Gumbel sample, written straight into pinned host
-      // buffers: replaces cat/2x linear/rand/log/argmax/3x D2H.
-      const int64_t seed =
-          greedy_ ? 0 : (int64_t)(seed_ctr_.fetch_add(1) * 0x9E3779B97F4A7C15ull);
-      trace("heads");
-      if (rows) {
-        fused_heads_sample_out(
-            x, rew, weights_[head_base_], weights_[head_base_ + 1],
-            weights_[head_base_ + 2], weights_[head_base_ + 3], b, greedy_,
-            seed, staging.h_action.data_ptr<int64_t>(),
-            staging.h_logits.data_ptr<float>(),
-            staging.h_base.data_ptr<float>());
-        marks.mark(kServeEnqueue);
-        stream.synchronize();
-        marks.mark(kServeSyncWait);
-        // Scatter into the rows, then wake each actor thread once.
-        const auto& reqs = batch.requests();
-        const size_t na = reqs[0].layout->n_env;
-        const int64_t A = staging.A;
-        const int64_t* ha = staging.h_action.data_ptr<int64_t>();
-        const float* hl = staging.h_logits.data_ptr<float>();
-        const float* hb = staging.h_base.data_ptr<float>();
-        for (int64_t r = 0; r < b; ++r) {
-          *reinterpret_cast<int64_t*>(reqs[r].leaf_ptr(na)) = ha[r];
-          std::memcpy(reqs[r].leaf_ptr(na + 1), hl + r * A, A * 4);
-          *reinterpret_cast<float*>(reqs[r].leaf_ptr(na + 2)) = hb[r];
-        }
-        const int64_t t_sync = timing ? now_us() : 0;
-        batch.complete_rows();
-        marks.mark(kServeFanout);
-        batcher_->count_row_batch();
-        if (staging.device_gather) batcher_->count_device_gather_batch();
-        batches_.fetch_add(1, std::memory_order_relaxed);
-        steps_.fetch_add(b, std::memory_order_relaxed);
-        if (timing) record_fused_timing(t_cat - t0, t_sync - t_cat);
-        if (warm_lock.owns_lock()) {
-          std::lock_guard<std::mutex> g(warm_mu_);
-          warmed_sizes_.insert(bq);
-        }
-        return;
+  // bf16 channels_last ResNet trunk, every conv on the MFMA template.
+  torch::Tensor trunk_deep_mfma(const ServeInputs& in,
+                                const std::vector<torch::Tensor>& wp) {
+    auto x8 = torch::empty({in.bp, 8, 84, 84},
+                           torch::TensorOptions().device(device_).dtype(
+                               torch::kBFloat16),
+                           torch::MemoryFormat::ChannelsLast);
+    x8.zero_();
+    x8.narrow(1, 0, in.C).copy_(in.frames, /*non_blocking=*/true);
+    x8.mul_(1.0f / 255.0f);
+    size_t wi = 0, pi = 0;
+    auto conv = [&](torch::Tensor t, int64_t ci, int64_t hw, int64_t co) {
+      auto o = tbamd::resnet_conv(t, wp[pi], weights_[wi + 1], ci, hw, co,
+                                  /*fwd=*/true);
+      ++pi;
+      wi += 2;
+      return o.permute({0, 3, 1, 2});
+    };
+    const int64_t widths[3] = {16, 32, 32};
+    int64_t hw = 84, ci = 8;
+    torch::Tensor t = x8;
+    for (int sec = 0; sec < 3; ++sec) {
+      t = conv(t, ci, hw, widths[sec]);
+      t = at::max_pool2d(t, 3, 2, 1);
+      hw = (hw + 1) / 2;
+      ci = widths[sec];
+      for (int res = 0; res < 2; ++res) {
+        torch::Tensor y = conv(at::relu(t), ci, hw, ci);
+        y = conv(at::relu(y), ci, hw, ci);
+        t = t + y;
       }
-      auto hs = fused_heads_sample(
-          x, rew, weights_[head_base_], weights_[head_base_ + 1],
-          weights_[head_base_ + 2], weights_[head_base_ + 3], b, greedy_,
-          seed);
-      trace("heads-sync");
-      marks.mark(kServeEnqueue);
-      stream.synchronize();
-      marks.mark(kServeSyncWait);
-      trace("heads-done");
-      int64_t t_fwd2 = timing ? now_us() : 0;
-      TensorNest::vector_t agent_out{
-          TensorNest(hs[0].reshape({1, b})),
-          TensorNest(hs[1].reshape({1, b, -1})),
-          TensorNest(hs[2].reshape({1, b})),
-      };
-      batch.set_outputs(TensorNest(TensorNest::vector_t{
-          TensorNest(std::move(agent_out)), TensorNest(TensorNest::vector_t{})}));
-      marks.mark(kServeFanout);
-      batches_.fetch_add(1, std::memory_order_relaxed);
-      steps_.fetch_add(b, std::memory_order_relaxed);
-      if (timing) record_fused_timing(t_cat - t0, t_fwd2 - t_cat);
-      if (warm_lock.owns_lock()) {
-        std::lock_guard<std::mutex> g(warm_mu_);
-        warmed_sizes_.insert(bq);
-      }
-      return;
     }
+    return at::relu(t).to(torch::kFloat32).reshape({in.bp, -1});
+  }
 
-    torch::Tensor core = at::cat({x, rew}, 1);
+  // ---- tails ----
+  // The one stream synchronise of a batch: after its last enqueue, before
+  // any host read of the outputs and any fan-out.
+  void synchronize(at::cuda::CUDAStream& stream, CpuMarks& marks) {
+    marks.mark(kServeEnqueue);
+    stream.synchronize();
+    marks.mark(kServeSyncWait);
+  }
+
+  int64_t next_seed() {
+    return greedy_
+               ? 0
+               : (int64_t)(seed_ctr_.fetch_add(1) * 0x9E3779B97F4A7C15ull);
+  }
+
+  // Fused heads + Gumbel sample written straight into this thread's pinned
+  // staging, scattered into the rows, then each actor thread woken once.
+  void tail_fused_rows(DynamicBatcher::Batch& batch, const ServeInputs& in,
+                       const torch::Tensor& x, at::cuda::CUDAStream& stream,
+                       RowStaging& staging, CpuMarks& marks) {
+    const int64_t b = in.b;
+    trace("heads");
+    fused_heads_sample_out(
+        x, in.rew, weights_[head_base_], weights_[head_base_ + 1],
+        weights_[head_base_ + 2], weights_[head_base_ + 3], b, greedy_,
+        next_seed(), staging.h_action.data_ptr<int64_t>(),
+        staging.h_logits.data_ptr<float>(), staging.h_base.data_ptr<float>());
+    synchronize(stream, marks);
+    const auto& reqs = batch.requests();
+    const size_t na = reqs[0].layout->n_env;
+    const int64_t A = staging.A;
+    const int64_t* ha = staging.h_action.data_ptr<int64_t>();
+    const float* hl = staging.h_logits.data_ptr<float>();
+    const float* hb = staging.h_base.data_ptr<float>();
+    // Typed writes: RowLayout::is_flagship_step vouches for the leaves.
+    for (int64_t r = 0; r < b; ++r) {
+      *reinterpret_cast<int64_t*>(reqs[r].leaf_ptr(na)) = ha[r];
+      std::memcpy(reqs[r].leaf_ptr(na + 1), hl + r * A, A * 4);
+      *reinterpret_cast<float*>(reqs[r].leaf_ptr(na + 2)) = hb[r];
+    }
+    marks.stamp(marks.t_sync);
+    batch.complete_rows();
+    marks.mark(kServeFanout);
+  }
+
+  // Fused heads + Gumbel sample, written straight into fresh pinned host
+  // tensors: replaces cat/2x linear/rand/log/argmax/3x D2H.
+  void tail_fused(DynamicBatcher::Batch& batch, const ServeInputs& in,
+                  const torch::Tensor& x, at::cuda::CUDAStream& stream,
+                  CpuMarks& marks) {
+    const int64_t b = in.b;
+    trace("heads");
+    auto hs = fused_heads_sample(
+        x, in.rew, weights_[head_base_], weights_[head_base_ + 1],
+        weights_[head_base_ + 2], weights_[head_base_ + 3], b, greedy_,
+        next_seed());
+    trace("heads-sync");
+    synchronize(stream, marks);
+    trace("heads-done");
+    marks.stamp(marks.t_sync);
+    TensorNest::vector_t agent_out{
+        TensorNest(hs[0].reshape({1, b})),
+        TensorNest(hs[1].reshape({1, b, -1})),
+        TensorNest(hs[2].reshape({1, b})),
+    };
+    batch.set_outputs(TensorNest(TensorNest::vector_t{
+        TensorNest(std::move(agent_out)), TensorNest(TensorNest::vector_t{})}));
+    marks.mark(kServeFanout);
+  }
+
+  // LSTM core (if any), ATen heads, D2H into pinned host tensors.
+  void tail_generic(DynamicBatcher::Batch& batch, const ServeInputs& in,
+                    const torch::Tensor& x, at::cuda::CUDAStream& stream,
+                    CpuMarks& marks) {
+    const int64_t b = in.b, bp = in.bp;
+    torch::Tensor core = at::cat({x, in.rew}, 1);
 
     std::vector<torch::Tensor> new_state_gpu;
     if (num_lstm_layers_ > 0) {
-      TORCH_CHECK(state.size() == 2, "lstm runner needs (h, c) state");
-      const int64_t L = state[0].size(0);
-      const int64_t H = state[0].size(2);
-      torch::Tensor nd = nd_gpu.narrow(0, 0, b).reshape({1, b, 1});
+      TORCH_CHECK(in.state.size() == 2, "lstm runner needs (h, c) state");
+      const int64_t L = in.state[0].size(0);
+      const int64_t H = in.state[0].size(2);
+      auto opts = torch::TensorOptions().device(device_);
+      torch::Tensor nd = in.notdone.narrow(0, 0, b).reshape({1, b, 1});
       auto pad_state = [&](const torch::Tensor& s) {
         torch::Tensor g = torch::zeros({L, bp, H}, opts.dtype(torch::kFloat32));
         g.narrow(1, 0, b).copy_(
             s.to(opts.dtype(torch::kFloat32), true) * nd);
         return g;
       };
-      torch::Tensor h = pad_state(state[0]);
-      torch::Tensor c = pad_state(state[1]);
+      torch::Tensor h = pad_state(in.state[0]);
+      torch::Tensor c = pad_state(in.state[1]);
       torch::Tensor layer_in = core;
       std::vector<torch::Tensor> hs, cs;
       for (int64_t l = 0; l < num_lstm_layers_; ++l) {
@@ -692,46 +724,61 @@ class InferenceRunner {
       out.copy_(t, /*non_blocking=*/true);
       return out;
     };
-    int64_t t_fwd = timing ? now_us() : 0;
+    marks.stamp(marks.t_fwd);
     torch::Tensor a_h = to_host(action);
     torch::Tensor l_h = to_host(logits);
     torch::Tensor b_h = to_host(baseline);
-    std::vector<torch::Tensor> state_h;
-    for (const auto& s : new_state_gpu) state_h.push_back(to_host(s));
-    marks.mark(kServeEnqueue);
-    stream.synchronize();
-    marks.mark(kServeSyncWait);
-    if (timing) {
-      const int64_t t_sync = now_us();
-      t_cat_us_.fetch_add(t_cat - t0, std::memory_order_relaxed);
-      t_fwd_us_.fetch_add(t_fwd - t_cat, std::memory_order_relaxed);
-      t_d2h_us_.fetch_add(t_sync - t_fwd, std::memory_order_relaxed);
-      const int64_t n = timed_batches_.fetch_add(1) + 1;
-      if (n % 500 == 0) {
-        fprintf(stderr,
-                "[serve timings over %lld batches] cat=%.0fus fwd=%.0fus "
-                "d2h+sync=%.0fus\n",
-                (long long)n, (double)t_cat_us_.load() / n,
-                (double)t_fwd_us_.load() / n, (double)t_d2h_us_.load() / n);
-      }
-    }
+    TensorNest::vector_t state_out;
+    for (const auto& s : new_state_gpu) state_out.emplace_back(to_host(s));
+    synchronize(stream, marks);
+    marks.stamp(marks.t_sync);
 
     TensorNest::vector_t agent_out{
         TensorNest(a_h.reshape({1, b})),
         TensorNest(l_h.reshape({1, b, -1})),
         TensorNest(b_h.reshape({1, b})),
     };
-    TensorNest::vector_t state_out;
-    for (const auto& s : state_h) state_out.emplace_back(s);
     batch.set_outputs(TensorNest(TensorNest::vector_t{
         TensorNest(std::move(agent_out)), TensorNest(std::move(state_out))}));
     marks.mark(kServeFanout);
+  }
 
+  // ---- epilogue ----
+  // The batch is delivered. `warmed` is its quantized size if it was served
+  // under the first-serve lock (still held here), else 0.
+  void finish(const ServeInputs& in, const RowStaging& staging,
+              const CpuMarks& marks, int64_t warmed) {
+    if (in.rows) {
+      batcher_->count_row_batch();
+      if (staging.device_gather) batcher_->count_device_gather_batch();
+    }
     batches_.fetch_add(1, std::memory_order_relaxed);
-    steps_.fetch_add(b, std::memory_order_relaxed);
-    if (warm_lock.owns_lock()) {
+    steps_.fetch_add(in.b, std::memory_order_relaxed);
+    if (warmed) {
       std::lock_guard<std::mutex> g(warm_mu_);
-      warmed_sizes_.insert(bq);
+      warmed_sizes_.insert(warmed);
+    }
+    if (!serve_timing_) return;
+    // The fused tails have no D2H of their own: forward and synchronise are
+    // one figure there.
+    const int64_t t_fwd = fused_heads_ ? marks.t_sync : marks.t_fwd;
+    t_cat_us_.fetch_add(marks.t_cat - marks.t0, std::memory_order_relaxed);
+    t_fwd_us_.fetch_add(t_fwd - marks.t_cat, std::memory_order_relaxed);
+    t_d2h_us_.fetch_add(marks.t_sync - t_fwd, std::memory_order_relaxed);
+    const int64_t n = timed_batches_.fetch_add(1) + 1;
+    if (n % 500 != 0) return;
+    const double cat = (double)t_cat_us_.load() / n;
+    const double fwd = (double)t_fwd_us_.load() / n;
+    if (fused_heads_) {
+      fprintf(stderr,
+              "[serve timings over %lld batches] cat=%.0fus "
+              "fwd+sync=%.0fus\n",
+              (long long)n, cat, fwd);
+    } else {
+      fprintf(stderr,
+              "[serve timings over %lld batches] cat=%.0fus fwd=%.0fus "
+              "d2h+sync=%.0fus\n",
+              (long long)n, cat, fwd, (double)t_d2h_us_.load() / n);
     }
   }
 
@@ -739,9 +786,7 @@ class InferenceRunner {
   torch::Tensor slab_frames_, slab_rew_, slab_done_;
   std::vector<int64_t> frame_shape_;
   std::mutex pack_mu_;
-  torch::Tensor w1p_, w2p_, w3p_;
-  std::vector<torch::Tensor> deep_packed_;
-  int64_t deep_packed_version_ = -1;
+  std::vector<torch::Tensor> packed_;  // see packed_weights
   int64_t packed_version_ = -1;
   std::atomic<int64_t> weights_version_{0};
   std::atomic<uint64_t> seed_ctr_{1};
@@ -749,11 +794,9 @@ class InferenceRunner {
   // comparison in scripts/inference_speed_profiling.py).
   const bool aten_only_ = std::getenv("TBAMD_RUNNER_ATEN") != nullptr;
   const bool serve_timing_ = std::getenv("TBAMD_SERVE_TIMINGS") != nullptr;
+  const bool trace_ = std::getenv("TBAMD_SERVE_TRACE") != nullptr;
   // TBAMD_ACTOR_FASTPATH=0: tensor serve code only (A/B against rows).
-  const bool legacy_serve_ = [] {
-    const char* v = std::getenv("TBAMD_ACTOR_FASTPATH");
-    return v != nullptr && std::string(v) == "0";
-  }();
+  const bool legacy_serve_ = !actor_fastpath_enabled();
   // TBAMD_ROW_GATHER=host|device forces either gather for every row batch
   // (A/B only). Default: what the pool's layout asks for, i.e. the device
   // gather in obs-slab mode and the host gather otherwise.
@@ -775,6 +818,8 @@ class InferenceRunner {
   const int64_t num_lstm_layers_;
   const bool greedy_;
   bool deep_ = false;
+  bool deep_mfma_ = false;    // deep trunk on the MFMA kernels (at 84x84)
+  bool fused_heads_ = false;  // fused heads tail, else LSTM/ATen heads
   size_t head_base_ = 8;
   size_t lstm_base_ = 12;
   torch::Device device_ = torch::kCPU;

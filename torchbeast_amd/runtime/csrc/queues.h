@@ -33,6 +33,7 @@
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
+#include <cstdlib>
 #include <cstring>
 #include <deque>
 #include <functional>
@@ -42,6 +43,7 @@
 #include <mutex>
 #include <optional>
 #include <stdexcept>
+#include <string>
 #include <vector>
 
 #include "nest.h"
@@ -55,6 +57,14 @@ inline int64_t now_us() {
   return std::chrono::duration_cast<std::chrono::microseconds>(
              std::chrono::steady_clock::now().time_since_epoch())
       .count();
+}
+
+// TBAMD_ACTOR_FASTPATH=0 (A/B runs only) keeps actors on the nest/promise
+// loops and the runner on the tensor serve code; anything else leaves the
+// row fast path on.
+inline bool actor_fastpath_enabled() {
+  const char* v = std::getenv("TBAMD_ACTOR_FASTPATH");
+  return !(v != nullptr && std::string(v) == "0");
 }
 
 // Lightweight perf counters (atomics; read via .stats() from Python).
@@ -888,6 +898,24 @@ struct RowLayout {
   bool leaf_matches(size_t i, const torch::Tensor& t) const {
     const RowLeaf& l = leaves[i];
     return t.scalar_type() == l.dtype && t.sizes().vec() == l.shape;
+  }
+
+  // Is a row the flagship step: env leaves (frame u8 [1, 1, C, H, W], reward
+  // f32, ...) and agent leaves (action i64, logits f32 [A], baseline f32)?
+  // The C++ runner reads a row's reward and writes its agent outputs through
+  // typed pointers on the strength of exactly these checks.
+  bool is_flagship_step(int64_t A) const {
+    if (n_env < 3 || leaves.size() != n_env + 3) return false;
+    const RowLeaf& frame = leaves[0];
+    const RowLeaf& reward = leaves[1];
+    const RowLeaf& action = leaves[n_env];
+    const RowLeaf& logits = leaves[n_env + 1];
+    const RowLeaf& baseline = leaves[n_env + 2];
+    return frame.dtype == torch::kUInt8 && frame.shape.size() == 5 &&
+           reward.dtype == torch::kFloat32 && reward.row_bytes == 4 &&
+           action.dtype == torch::kInt64 && action.row_bytes == 8 &&
+           logits.dtype == torch::kFloat32 && logits.row_bytes == 4 * A &&
+           baseline.dtype == torch::kFloat32 && baseline.row_bytes == 4;
   }
 };
 
