@@ -56,6 +56,15 @@ def add_optimizer_flags(parser: argparse.ArgumentParser):
     return parser
 
 
+def add_runtime_flags(parser: argparse.ArgumentParser):
+    parser.add_argument("--recurrent_rows", action="store_true",
+                        help="Keep the LSTM state of every env stream in the "
+                             "actor pool's pinned state rows, served in "
+                             "place by the C++ runner's LSTM kernels "
+                             "(needs --use_lstm and the C++ runner).")
+    return parser
+
+
 def parse_synthetic_env_spec(env: str):
     """Parse 'synthetic[:CxHxW[:A]]' -> (shape, num_actions) or None."""
     if not env.startswith("synthetic"):

@@ -81,6 +81,7 @@ def make_parser():
                         help="Serve inference from Python threads instead of "
                              "the C++ engine (always the case for --model "
                              "deep or on CPU).")
+    tbflags.add_runtime_flags(parser)
     tbflags.add_loss_flags(parser)
     tbflags.add_optimizer_flags(parser)
     return parser
@@ -522,6 +523,11 @@ def train(flags):  # noqa: C901
             flags.envs_per_thread if flags.envs_per_thread > 0
             else (16 if tbflags.parse_synthetic_env_spec(flags.env) is not None
                   else 1)),
+        # State rows only where the C++ runner serves an LSTM model; None
+        # leaves the choice to TBAMD_RECURRENT_ROWS.
+        recurrent_rows=(True if (getattr(flags, "recurrent_rows", False)
+                                 and use_cpp_inference and flags.use_lstm)
+                        else None),
     )
 
     pool_failure = []

@@ -9,10 +9,12 @@
 //
 // Two implementations:
 // - loop_rows (default whenever the pool has a rollout budget; in obs-slab
-//   mode only for a stateless agent, whose batches the runner then gathers
-//   from the rows on the GPU): every env stream holds a pinned slab slot
-//   carved into [T+1, 1, ...] columns and fills it row by row in place.
-//   Envs write their
+//   mode only for a stateless agent, or a recurrent one with state rows
+//   (recurrent_rows / TBAMD_RECURRENT_ROWS=1, off by default), whose batches
+//   the runner then gathers from the rows on the GPU): every env stream
+//   holds a pinned slab slot carved into [T+1, 1, ...] columns and fills it
+//   row by row in place. With state rows the (h, c) state of every stream
+//   lives in one pinned block as well (StateBlock, queues.h). Envs write their
 //   step into the row (EnvConnection::step_into), requests are row PODs
 //   submitted under one lock per sweep, and the thread blocks on its own
 //   ActorMailbox (queues.h) -- no per-step tensors, promises or polling. A
@@ -47,7 +49,8 @@ class ActorPool {
             std::vector<std::string> env_server_addresses,
             TensorNest initial_agent_state, int64_t seed_base = 0,
             bool use_obs_slab = false, int64_t rollout_budget_mb = 0,
-            int64_t envs_per_thread = 1)
+            int64_t envs_per_thread = 1,
+            std::optional<bool> recurrent_rows = std::nullopt)
       : unroll_length_(unroll_length),
         learner_queue_(std::move(learner_queue)),
         inference_batcher_(std::move(inference_batcher)),
@@ -94,15 +97,41 @@ class ActorPool {
     }
     // TBAMD_ACTOR_FASTPATH=0 keeps the nest/promise loops below (A/B only).
     const bool fastpath = actor_fastpath_enabled();
-    // Obs-slab mode has a row form for stateless agents: the frame is
-    // written once, into its rollout row, and the runner gathers the batch
-    // from the rows on the GPU (RowLayout::device_gather). No second slab,
-    // no slot ids. A recurrent agent on rows would fall back to a host
-    // gather of its frames, so it keeps the slot-id loops.
+    // State rows (opt-in): an (h, c) agent state lives in one pinned block
+    // of the pool's (StateBlock, queues.h) instead of per-request tensors,
+    // and the C++ runner's LSTM serve kernels read and write it in place.
+    // recurrent_rows = true insists (a state of another form is an error);
+    // unset, TBAMD_RECURRENT_ROWS=1 asks for it where the state allows.
+    int64_t state_L = 0, state_H = 0;
+    const bool state_fits =
+        StateBlock::describes(initial_agent_state_, &state_L, &state_H);
+    if (recurrent_rows.has_value()) {
+      if (*recurrent_rows && !state_fits) {
+        throw std::invalid_argument(
+            "recurrent_rows needs an agent state (h, c) of contiguous "
+            "float32 [L, 1, H] tensors");
+      }
+      recurrent_rows_ = *recurrent_rows;
+    } else {
+      const char* v = std::getenv("TBAMD_RECURRENT_ROWS");
+      recurrent_rows_ = v != nullptr && std::string(v) == "1" && state_fits;
+    }
+    // Obs-slab mode has a row form: the frame is written once, into its
+    // rollout row, and the runner gathers the batch from the rows on the GPU
+    // (RowLayout::device_gather). No second slab, no slot ids. For a
+    // stateless agent always; for a recurrent one with state rows. Without
+    // them a recurrent agent on rows would fall back to a host gather of its
+    // frames, so it keeps the slot-id loops.
     device_gather_ = use_obs_slab_ && rollout_pool_ != nullptr && fastpath &&
-                     initial_agent_state_.empty();
+                     (initial_agent_state_.empty() || recurrent_rows_);
     use_rows_ = rollout_pool_ != nullptr && fastpath &&
                 (!use_obs_slab_ || device_gather_);
+    if (recurrent_rows_ && use_rows_) {
+      // Once, before any actor thread runs: a fresh pinned allocation
+      // synchronises the device.
+      state_block_ =
+          StateBlock::make((int64_t)addresses_.size(), state_L, state_H);
+    }
   }
 
   // Pinned observation slab (slot per actor). Valid once the first env has
@@ -392,6 +421,26 @@ class ActorPool {
         layout.agent_template.pack_from(std::move(agent_views))});
   }
 
+  // State rows: the state answering a stream's first step (a nest request)
+  // becomes half 0 of the stream, its current half.
+  void store_first_state(ActorMailbox& mailbox, size_t i,
+                         const TensorNest& state) const {
+    int64_t L = 0, H = 0;
+    const TensorNest host = state.map([](const torch::Tensor& t) {
+      return (t.is_cuda() ? t.cpu() : t).contiguous();
+    });
+    if (!StateBlock::describes(host, &L, &H) || L != state_block_->L ||
+        H != state_block_->H) {
+      throw std::runtime_error(
+          "first step's agent state disagrees with the pool's state rows");
+    }
+    float* dst = state_block_->half(mailbox.stream_index[i], 0);
+    const int64_t n = L * H;
+    std::memcpy(dst, host.vector()[0].leaf().data_ptr<float>(), n * 4);
+    std::memcpy(dst + n, host.vector()[1].leaf().data_ptr<float>(), n * 4);
+    mailbox.cur_half[i] = 0;
+  }
+
   // One thread, several env streams, each filling its rollout slot in
   // place. Requests are row PODs submitted under one lock per sweep; the
   // thread blocks on its own mailbox, drains every ready env, steps those
@@ -401,8 +450,24 @@ class ActorPool {
     const int64_t T = unroll_length_;
     std::vector<RowStream> streams(n);
     auto mailbox = std::make_shared<ActorMailbox>();
-    mailbox->state.assign(n, initial_agent_state_);
     mailbox->slab = rollout_pool_;
+    const bool state_rows = state_block_ != nullptr;
+    if (!state_rows) {
+      mailbox->state.assign(n, initial_agent_state_);
+    } else {
+      // mailbox->state stays empty: the states are halves of the block.
+      mailbox->state_block = state_block_;
+      mailbox->stream_index.resize(n);
+      mailbox->cur_half.assign(n, 0);
+      mailbox->half_views.reserve(2 * n);
+      for (size_t i = 0; i < n; ++i) {
+        mailbox->stream_index[i] = (int32_t)(lo + i);
+        for (int half = 0; half < 2; ++half) {
+          mailbox->half_views.push_back(
+              state_block_->views((int64_t)(lo + i), half));
+        }
+      }
+    }
 
     // The first step of every stream travels as a nest request with a
     // promise: its answer shows the agent-output dtypes and shapes the
@@ -430,7 +495,11 @@ class ActorPool {
             "inference must return ((action, ...), agent_state)");
       }
       const TensorNest& agent_outputs = result.vector()[0];
-      mailbox->state[i] = result.vector()[1];
+      if (state_rows) {
+        store_first_state(*mailbox, i, result.vector()[1]);
+      } else {
+        mailbox->state[i] = result.vector()[1];
+      }
       layout = ensure_layout(first_env[i], agent_outputs);
       acquire_row_slot(s, *layout);
       size_t leaf = 0;
@@ -505,7 +574,16 @@ class ActorPool {
         requests.clear();
         for (int32_t i : ready) {
           RowStream& s = streams[i];
-          s.state_before = mailbox->state[i];
+          if (!state_rows) {
+            s.state_before = mailbox->state[i];
+          } else if (s.t == T) {
+            // Only row T's state is ever recorded (as the next rollout's
+            // initial state), and the block goes on changing under it: a
+            // real copy, once per rollout.
+            s.state_before =
+                mailbox->half_views[2 * i + mailbox->cur_half[i]].map(
+                    [](const torch::Tensor& t) { return t.clone(); });
+          }
           DynamicBatcher::Request r;
           r.batch_size = 1;
           r.mailbox = mailbox;
@@ -665,6 +743,8 @@ class ActorPool {
   std::shared_ptr<PinnedSlabPool> rollout_pool_;
   bool use_rows_ = false;
   bool device_gather_ = false;  // obs-slab mode on rows, see the constructor
+  bool recurrent_rows_ = false;  // state rows asked for, see the constructor
+  std::shared_ptr<StateBlock> state_block_;  // set when they are in use
   std::mutex layout_mu_;
   std::shared_ptr<const RowLayout> layout_;
   std::atomic<int64_t> rollout_slot_bytes_{0};

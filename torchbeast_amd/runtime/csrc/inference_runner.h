@@ -18,7 +18,10 @@
 //           until mark_weights_dirty().
 //   tail    heads, the batch's one stream synchronise, delivery: fused heads
 //           scattered into the rows (tail_fused_rows) or into pinned tensors
-//           (tail_fused), or LSTM core + ATen heads + D2H (tail_generic).
+//           (tail_fused), the LSTM serve kernels on the pool's pinned state
+//           rows plus the heads, scattered into the rows (tail_lstm_rows,
+//           for pools with recurrent_rows), or LSTM core + ATen heads + D2H
+//           (tail_generic).
 //   finish  counters, warmed batch sizes, TBAMD_SERVE_TIMINGS.
 // Behavior-model weights are VIEWS of the learner's flat actor buffer, so
 // weight sync stays one flat device copy with no runner involvement.
@@ -79,6 +82,23 @@ class InferenceRunner {
                    weights_[head_base_].size(0) <= 64 &&
                    weights_[head_base_].size(1) ==
                        weights_[head_base_ - 2].size(0) + 1;
+    // The LSTM serve kernels take [fc output, reward] into layer 0 and hand
+    // the last layer's h to the heads. A core too wide for the layer
+    // kernel's LDS tile is served through get_inputs() / tail_generic.
+    lstm_rows_ = !aten_only_ && num_lstm_layers_ > 0 &&
+                 weights_[head_base_].size(0) <= 64;
+    for (int64_t l = 0; l < num_lstm_layers_ && lstm_rows_; ++l) {
+      const auto& w_ih = weights_[lstm_base_ + 4 * l];
+      const auto& w_hh = weights_[lstm_base_ + 4 * l + 1];
+      const int64_t H = weights_[lstm_base_ + 1].size(1);
+      const int64_t I = l == 0 ? weights_[head_base_ - 2].size(0) + 1 : H;
+      lstm_rows_ = w_ih.dim() == 2 && w_hh.dim() == 2 && w_hh.size(1) == H &&
+                   w_ih.size(1) == I && w_ih.size(0) == 4 * H &&
+                   w_hh.size(0) == 4 * H &&
+                   w_ih.scalar_type() == torch::kFloat32 &&
+                   weights_[head_base_].size(1) == H &&
+                   lstm_serve_layer_fits(I, H);
+    }
   }
 
   ~InferenceRunner() { stop(); }
@@ -206,6 +226,17 @@ class InferenceRunner {
     torch::Tensor h_frames, h_rew, d_frames, d_rew;  // inputs
     torch::Tensor h_table;                           // pinned, device gather
     torch::Tensor h_action, h_logits, h_base;        // pinned outputs
+    // Recurrent row batches (tail_lstm_rows): the state table ([3, cap]
+    // addresses: state in, state out, done byte; pinned), h of every layer
+    // ([cap, H] each, device) and this thread's packed LSTM weights, kept
+    // until mark_weights_dirty().
+    int64_t lstm_cap = 0;
+    torch::Tensor h_state_table;
+    std::vector<torch::Tensor> d_h;
+    torch::Tensor d_state;  // [cap, 2 L H]: the batch's masked old state
+    std::vector<LstmLayerPack> lstm_pack;
+    int64_t lstm_pack_version = -1;
+    std::vector<uintptr_t> table_scratch;
   };
 
   // What the input stage hands to the trunk and the tail.
@@ -218,6 +249,7 @@ class InferenceRunner {
     std::vector<torch::Tensor> state;  // [] or h, c [L, b, H]
     TensorNest source;  // the batcher's nest the copies above read from
     bool rows = false;  // outputs go back through RowStaging into the rows
+    bool state_rows = false;  // ... and the LSTM state lives in state rows
   };
 
   // Compute batches are multiples of 64 so kernel/solution caches see a
@@ -266,8 +298,34 @@ class InferenceRunner {
   bool rows_servable(const DynamicBatcher::Batch& batch) const {
     if (!batch.all_rows() || !fused_heads_ || legacy_serve_) return false;
     const auto& req = batch.requests()[0];
-    return req.state().empty() &&
+    return !req.mailbox->has_state_rows() && req.state().empty() &&
            req.layout->is_flagship_step(weights_[head_base_].size(0));
+  }
+
+  // The recurrent case: an LSTM model, every request a row of the flagship
+  // step layout (with a one-byte done leaf) whose mailbox carries the
+  // pool's pinned state block, of the weights' L and H. Anything else (an
+  // unpinned block under TBAMD_NO_PIN, for one) goes through get_inputs().
+  bool state_rows_servable(const DynamicBatcher::Batch& batch) const {
+    if (!batch.all_rows() || !lstm_rows_ || legacy_serve_) return false;
+    const auto& reqs = batch.requests();
+    const RowLayout& l = *reqs[0].layout;
+    if (!l.is_flagship_step(weights_[head_base_].size(0)) ||
+        l.leaves[2].dtype != torch::kBool || l.leaves[2].row_bytes != 1) {
+      return false;
+    }
+    const StateBlock* block = reqs[0].mailbox->state_block.get();
+    if (block == nullptr || !block->pinned || block->L != num_lstm_layers_ ||
+        block->H != weights_[lstm_base_ + 1].size(1)) {
+      return false;
+    }
+    const ActorMailbox* last = nullptr;
+    for (const auto& r : reqs) {
+      if (r.mailbox.get() == last) continue;
+      last = r.mailbox.get();
+      if (last->state_block.get() != block) return false;
+    }
+    return true;
   }
 
   static void hip_check(hipError_t e, const char* what) {
@@ -288,6 +346,9 @@ class InferenceRunner {
     ServeInputs in;
     if (rows_servable(batch)) {
       in = inputs_from_rows(batch, stream, staging, marks);
+    } else if (state_rows_servable(batch)) {
+      in = inputs_from_rows(batch, stream, staging, marks);
+      in.state_rows = true;
     } else {
       // nest = ((frame, reward, done, ...), state)  [classic requests]
       //      = (slot_ids, state)                     [obs-slab requests]
@@ -316,7 +377,9 @@ class InferenceRunner {
       if (is_new) warm_lock = std::unique_lock<std::mutex>(serve_mu_);
     }
     torch::Tensor x = trunk(in, stream);
-    if (!fused_heads_) {
+    if (in.state_rows) {
+      tail_lstm_rows(batch, in, x, stream, staging, marks);
+    } else if (!fused_heads_) {
       tail_generic(batch, in, x, stream, marks);
     } else if (in.rows) {
       tail_fused_rows(batch, in, x, stream, staging, marks);
@@ -610,7 +673,16 @@ class InferenceRunner {
         next_seed(), staging.h_action.data_ptr<int64_t>(),
         staging.h_logits.data_ptr<float>(), staging.h_base.data_ptr<float>());
     synchronize(stream, marks);
-    const auto& reqs = batch.requests();
+    scatter_staged_outputs(batch.requests(), staging, b);
+    marks.stamp(marks.t_sync);
+    batch.complete_rows();
+    marks.mark(kServeFanout);
+  }
+
+  // The pinned staging's action / logits / baseline into the rows.
+  static void scatter_staged_outputs(
+      const std::vector<DynamicBatcher::Request>& reqs,
+      const RowStaging& staging, int64_t b) {
     const size_t na = reqs[0].layout->n_env;
     const int64_t A = staging.A;
     const int64_t* ha = staging.h_action.data_ptr<int64_t>();
@@ -622,6 +694,99 @@ class InferenceRunner {
       std::memcpy(reqs[r].leaf_ptr(na + 1), hl + r * A, A * 4);
       *reinterpret_cast<float*>(reqs[r].leaf_ptr(na + 2)) = hb[r];
     }
+  }
+
+  // Table, per-layer h and weight pack of the recurrent tail: allocated when
+  // the staging's capacity changes, repacked after mark_weights_dirty().
+  // Each serve thread packs for itself, on its own stream: stream order
+  // alone makes the pack complete before the kernels read it.
+  void ensure_lstm_staging(RowStaging& st) {
+    const int64_t H = weights_[lstm_base_ + 1].size(1);
+    if (st.lstm_cap != st.cap) {
+      st.h_state_table = torch::zeros(
+          {3, st.cap},
+          torch::TensorOptions().dtype(torch::kInt64).pinned_memory(true));
+      st.d_state = torch::zeros(
+          {st.cap, 2 * num_lstm_layers_ * H},
+          torch::TensorOptions().device(device_).dtype(torch::kFloat32));
+      st.d_h.clear();
+      for (int64_t l = 0; l < num_lstm_layers_; ++l) {
+        st.d_h.push_back(torch::zeros(
+            {st.cap, H},
+            torch::TensorOptions().device(device_).dtype(torch::kFloat32)));
+      }
+      st.lstm_cap = st.cap;
+    }
+    const int64_t v = weights_version_.load();
+    if (st.lstm_pack_version != v) {
+      st.lstm_pack.clear();
+      for (int64_t l = 0; l < num_lstm_layers_; ++l) {
+        st.lstm_pack.push_back(pack_lstm_layer(
+            weights_[lstm_base_ + 4 * l], weights_[lstm_base_ + 4 * l + 1],
+            weights_[lstm_base_ + 4 * l + 2],
+            weights_[lstm_base_ + 4 * l + 3]));
+      }
+      st.lstm_pack_version = v;
+    }
+  }
+
+  // Recurrent row batch: one lstm_serve_layer kernel per layer, reading
+  // each request's (h, c) from its stream's current half of the pool's
+  // state block and writing the new state into the other half, then the
+  // heads on the last layer's h, written into this thread's pinned staging
+  // and scattered into the rows. No ATen op, no tensor allocated. The new
+  // states are in the block when the synchronise returns; complete_rows()
+  // swaps the halves.
+  void tail_lstm_rows(DynamicBatcher::Batch& batch, const ServeInputs& in,
+                      const torch::Tensor& x, at::cuda::CUDAStream& stream,
+                      RowStaging& staging, CpuMarks& marks) {
+    const int64_t b = in.b;
+    const auto& reqs = batch.requests();
+    ensure_lstm_staging(staging);
+    const StateBlock& block = *reqs[0].mailbox->state_block;
+    const SlabGeometry slab = reqs[0].mailbox->slab->geometry();
+    // The table is written only here, and only with checked addresses.
+    int64_t* table = staging.h_state_table.data_ptr<int64_t>();
+    auto** in_tab = reinterpret_cast<const float**>(table);
+    auto** out_tab = reinterpret_cast<float**>(table + staging.cap);
+    auto** done_tab =
+        reinterpret_cast<const uint8_t**>(table + 2 * staging.cap);
+    build_state_table(
+        b,
+        [&reqs](int64_t r) {
+          return reqs[r].mailbox->state_in(reqs[r].env_index);
+        },
+        [&reqs](int64_t r) {
+          return reqs[r].mailbox->state_out(reqs[r].env_index);
+        },
+        [&reqs](int64_t r) { return reqs[r].leaf_ptr(2); },
+        block.half_floats(), block.base(), block.used_bytes(), slab.base,
+        slab.total_bytes, staging.table_scratch, in_tab, out_tab, done_tab);
+    trace("lstm");
+    const int64_t L = num_lstm_layers_;
+    const int64_t H = block.H;
+    TORCH_CHECK(x.is_contiguous() && x.scalar_type() == torch::kFloat32 &&
+                    x.size(0) >= b,
+                "lstm tail: trunk output must be contiguous f32 [bp, D]");
+    launch_lstm_stage_state(in_tab, done_tab, b, block.half_floats(),
+                            staging.d_state.data_ptr<float>());
+    for (int64_t l = 0; l < L; ++l) {
+      launch_lstm_serve_layer(
+          out_tab, staging.d_state.data_ptr<float>(),
+          l == 0 ? x.data_ptr<float>() : staging.d_h[l - 1].data_ptr<float>(),
+          l == 0 ? x.size(1) : H,
+          l == 0 ? in.rew.data_ptr<float>() : nullptr, staging.lstm_pack[l], b,
+          l, L, staging.d_h[l].data_ptr<float>());
+    }
+    launch_heads_sample(
+        staging.d_h[L - 1].data_ptr<float>(), nullptr, H,
+        weights_[head_base_], weights_[head_base_ + 1],
+        weights_[head_base_ + 2], weights_[head_base_ + 3], b, greedy_,
+        next_seed(), staging.h_action.data_ptr<int64_t>(),
+        staging.h_logits.data_ptr<float>(), staging.h_base.data_ptr<float>());
+    marks.stamp(marks.t_fwd);
+    synchronize(stream, marks);
+    scatter_staged_outputs(reqs, staging, b);
     marks.stamp(marks.t_sync);
     batch.complete_rows();
     marks.mark(kServeFanout);
@@ -751,6 +916,7 @@ class InferenceRunner {
     if (in.rows) {
       batcher_->count_row_batch();
       if (staging.device_gather) batcher_->count_device_gather_batch();
+      if (in.state_rows) batcher_->count_state_row_batch();
     }
     batches_.fetch_add(1, std::memory_order_relaxed);
     steps_.fetch_add(in.b, std::memory_order_relaxed);
@@ -820,6 +986,7 @@ class InferenceRunner {
   bool deep_ = false;
   bool deep_mfma_ = false;    // deep trunk on the MFMA kernels (at 84x84)
   bool fused_heads_ = false;  // fused heads tail, else LSTM/ATen heads
+  bool lstm_rows_ = false;    // LSTM serve kernels fit this model's core
   size_t head_base_ = 8;
   size_t lstm_base_ = 12;
   torch::Device device_ = torch::kCPU;

@@ -305,6 +305,59 @@ PYBIND11_MODULE(_tbruntime, m) {
       py::arg("slab_base"), py::arg("slab_bytes"), py::arg("frame_addrs"),
       py::arg("reward_addrs"), py::arg("fsz"));
 
+  // ---- LSTM serve step on state rows ----
+  // Test-only: the layer kernels and the heads on caller-made tensors.
+  m.def("lstm_serve_step", &lstm_serve_step, py::arg("x"), py::arg("rew"),
+        py::arg("lstm_weights"), py::arg("policy_w"), py::arg("policy_b"),
+        py::arg("base_w"), py::arg("base_b"), py::arg("state_block"),
+        py::arg("in_offsets"), py::arg("out_offsets"), py::arg("done_slab"),
+        py::arg("done_offsets"), py::arg("cap"), py::arg("greedy") = true,
+        py::arg("seed") = 0);
+  // Test-only: build_state_table() over plain addresses (never
+  // dereferenced). Returns (state-in, state-out, done pointers).
+  m.def(
+      "build_state_table",
+      [](uint64_t state_base, int64_t state_bytes, uint64_t slab_base,
+         int64_t slab_bytes, std::vector<uint64_t> in_addrs,
+         std::vector<uint64_t> out_addrs, std::vector<uint64_t> done_addrs,
+         int64_t n_floats) {
+        if (in_addrs.size() != out_addrs.size() ||
+            in_addrs.size() != done_addrs.size()) {
+          throw std::invalid_argument(
+              "one state-out and one done address per state-in address");
+        }
+        const int64_t b = (int64_t)in_addrs.size();
+        const size_t n = (size_t)std::max<int64_t>(b, 1);
+        std::vector<const float*> it(n);
+        std::vector<float*> ot(n);
+        std::vector<const uint8_t*> dt(n);
+        std::vector<uintptr_t> scratch;
+        build_state_table(
+            b,
+            [&](int64_t r) {
+              return reinterpret_cast<const uint8_t*>(in_addrs[r]);
+            },
+            [&](int64_t r) {
+              return reinterpret_cast<const uint8_t*>(out_addrs[r]);
+            },
+            [&](int64_t r) {
+              return reinterpret_cast<const uint8_t*>(done_addrs[r]);
+            },
+            n_floats, reinterpret_cast<const void*>(state_base), state_bytes,
+            reinterpret_cast<const uint8_t*>(slab_base), slab_bytes, scratch,
+            it.data(), ot.data(), dt.data());
+        std::vector<uint64_t> io(b), oo(b), dd(b);
+        for (int64_t r = 0; r < b; ++r) {
+          io[r] = reinterpret_cast<uintptr_t>(it[r]);
+          oo[r] = reinterpret_cast<uintptr_t>(ot[r]);
+          dd[r] = reinterpret_cast<uintptr_t>(dt[r]);
+        }
+        return std::make_tuple(io, oo, dd);
+      },
+      py::arg("state_base"), py::arg("state_bytes"), py::arg("slab_base"),
+      py::arg("slab_bytes"), py::arg("in_addrs"), py::arg("out_addrs"),
+      py::arg("done_addrs"), py::arg("n_floats"));
+
   // ---- BatchingQueue ----
   py::class_<BatchingQueue, std::shared_ptr<BatchingQueue>>(m, "BatchingQueue")
       .def(py::init<int64_t, std::optional<int64_t>, std::optional<int64_t>,
@@ -388,13 +441,15 @@ PYBIND11_MODULE(_tbruntime, m) {
   py::class_<ActorPool, std::shared_ptr<ActorPool>>(m, "ActorPool")
       .def(py::init<int64_t, std::shared_ptr<BatchingQueue>,
                     std::shared_ptr<DynamicBatcher>, std::vector<std::string>,
-                    TensorNest, int64_t, bool, int64_t, int64_t>(),
+                    TensorNest, int64_t, bool, int64_t, int64_t,
+                    std::optional<bool>>(),
            py::arg("unroll_length"), py::arg("learner_queue"),
            py::arg("inference_batcher"), py::arg("env_server_addresses"),
            py::arg("initial_agent_state"), py::arg("seed_base") = 0,
            py::arg("use_obs_slab") = false,
            py::arg("rollout_budget_mb") = 0,
-           py::arg("envs_per_thread") = 1)
+           py::arg("envs_per_thread") = 1,
+           py::arg("recurrent_rows") = std::nullopt)
       .def("run",
            [](ActorPool& pool) {
              DaemonGilRelease release;

@@ -919,11 +919,94 @@ struct RowLayout {
   }
 };
 
+// State rows: the recurrent state of every env stream of a pool in ONE
+// block, [n_streams, 2 halves, 2 (h, c), L, H] f32, pinned when a GPU is
+// there so that the serve kernels read and write it in place. A stream's
+// state lives in its current half; whoever answers a row request writes the
+// new state into the other half, and the halves swap when the request is
+// posted (Batch::complete_rows), so a writer never touches what a reader of
+// the same step reads. Allocated once, with a quantised size: a fresh
+// pinned allocation synchronises the device.
+struct StateBlock {
+  torch::Tensor storage;  // f32, at least n_streams * 4 * L * H elements
+  int64_t n_streams = 0, L = 0, H = 0;
+  bool pinned = false;
+
+  // Is `state` a pair (h, c) of contiguous f32 [L, 1, H] tensors?
+  static bool describes(const TensorNest& state, int64_t* L, int64_t* H) {
+    if (!state.is_vector() || state.vector().size() != 2) return false;
+    const auto& v = state.vector();
+    if (!v[0].is_leaf() || !v[1].is_leaf()) return false;
+    const torch::Tensor& h = v[0].leaf();
+    const torch::Tensor& c = v[1].leaf();
+    for (const torch::Tensor* t : {&h, &c}) {
+      if (!t->defined() || !t->device().is_cpu() ||
+          t->scalar_type() != torch::kFloat32 || t->dim() != 3 ||
+          t->size(1) != 1 || t->size(0) < 1 || t->size(2) < 1 ||
+          !t->is_contiguous()) {
+        return false;
+      }
+    }
+    if (h.sizes() != c.sizes()) return false;
+    *L = h.size(0);
+    *H = h.size(2);
+    return true;
+  }
+
+  static std::shared_ptr<StateBlock> make(int64_t n_streams, int64_t L,
+                                          int64_t H) {
+    auto out = std::make_shared<StateBlock>();
+    out->n_streams = n_streams;
+    out->L = L;
+    out->H = H;
+    out->pinned = pinned_memory_wanted();
+    // Quantised to 64 KiB.
+    const int64_t quantum = 16384;
+    const int64_t numel =
+        (n_streams * 4 * L * H + quantum - 1) / quantum * quantum;
+    out->storage = torch::zeros(
+        {numel}, torch::TensorOptions().dtype(torch::kFloat32).pinned_memory(
+                     out->pinned));
+    return out;
+  }
+
+  // Can `state` (an answer's state slice: any device, any strides) be
+  // copied into a half: an (h, c) pair of f32 [L, 1, H] tensors?
+  bool takes(const TensorNest& state) const {
+    if (!state.is_vector() || state.vector().size() != 2) return false;
+    for (const auto& leaf : state.vector()) {
+      if (!leaf.is_leaf() || !leaf.leaf().defined()) return false;
+      const torch::Tensor& t = leaf.leaf();
+      if (t.scalar_type() != torch::kFloat32 || t.dim() != 3 ||
+          t.size(0) != L || t.size(1) != 1 || t.size(2) != H) {
+        return false;
+      }
+    }
+    return true;
+  }
+
+  int64_t half_floats() const { return 2 * L * H; }
+  float* base() const { return storage.data_ptr<float>(); }
+  int64_t used_bytes() const { return n_streams * 2 * half_floats() * 4; }
+  float* half(int64_t stream, int half) const {
+    return base() + (stream * 2 + half) * half_floats();
+  }
+  // (h, c) views [L, 1, H] of one half; they keep the block alive.
+  TensorNest views(int64_t stream, int half) const {
+    const int64_t off = (stream * 2 + half) * half_floats();
+    return TensorNest(TensorNest::vector_t{
+        TensorNest(storage.narrow(0, off, L * H).view({L, 1, H})),
+        TensorNest(storage.narrow(0, off + L * H, L * H).view({L, 1, H}))});
+  }
+};
+
 // Completion queue of one actor thread, shared with every request of that
 // thread still in flight (so a serve thread can never post into a dead
 // actor thread's memory). state[i] is env i's agent state: read by the
 // server as the request's input state, replaced by the new state before i
-// is posted to `ready`.
+// is posted to `ready`. With state rows (state_block set) the state is not
+// replaced: half_views[2 * i + cur_half[i]] is env i's state, the answer is
+// written into the other half and cur_half[i] flips before i is posted.
 struct ActorMailbox {
   std::mutex mu;
   std::condition_variable cv;
@@ -936,6 +1019,19 @@ struct ActorMailbox {
   // The slab the rows point into: kept alive for requests in flight, and
   // asked for its bounds by whoever hands row addresses to the GPU.
   std::shared_ptr<PinnedSlabPool> slab;
+  // State rows (see StateBlock); all empty without them.
+  std::shared_ptr<StateBlock> state_block;
+  std::vector<int32_t> stream_index;    // env i's stream in the block
+  std::vector<uint8_t> cur_half;        // env i's current half
+  std::vector<TensorNest> half_views;   // [2 * i + half]
+
+  bool has_state_rows() const { return state_block != nullptr; }
+  float* state_in(int32_t i) const {
+    return state_block->half(stream_index[i], cur_half[i]);
+  }
+  float* state_out(int32_t i) const {
+    return state_block->half(stream_index[i], cur_half[i] ^ 1);
+  }
 
   int64_t outstanding = 0;  // requests submitted and not yet answered
 
@@ -1001,7 +1097,15 @@ class DynamicBatcher {
       const RowLeaf& l = layout->leaves[leaf];
       return slot_base + l.offset + (int64_t)row * l.row_bytes;
     }
-    const TensorNest& state() const { return mailbox->state[env_index]; }
+    // The agent state this request is to be answered from: with state rows
+    // an (h, c) nest of views of the stream's current half.
+    const TensorNest& state() const {
+      if (mailbox->has_state_rows()) {
+        return mailbox
+            ->half_views[2 * env_index + mailbox->cur_half[env_index]];
+      }
+      return mailbox->state[env_index];
+    }
     // The env leaves of the row as a [1, 1, ...] nest of views.
     TensorNest env_nest() const {
       std::vector<torch::Tensor> leaves;
@@ -1151,7 +1255,13 @@ class DynamicBatcher {
         std::vector<std::pair<ActorMailbox*, int32_t>> order;
         order.reserve(n_rows_);
         for (const auto& r : requests_) {
-          if (r.is_row()) order.emplace_back(r.mailbox.get(), r.env_index);
+          if (!r.is_row()) continue;
+          // State rows: the answer's state sits in the other half. The
+          // mailbox lock taken by post() publishes the flip to the actor.
+          if (r.mailbox->has_state_rows()) {
+            r.mailbox->cur_half[r.env_index] ^= 1;
+          }
+          order.emplace_back(r.mailbox.get(), r.env_index);
         }
         std::sort(order.begin(), order.end());
         std::vector<int32_t> idx;
@@ -1234,6 +1344,12 @@ class DynamicBatcher {
             "agent outputs have fewer leaves than the rollout slots were "
             "carved for");
       }
+      if (req.mailbox->has_state_rows() &&
+          !req.mailbox->state_block->takes(slice.vector()[1])) {
+        throw std::invalid_argument(
+            "agent state disagrees with the (h, c) [L, 1, H] float32 state "
+            "rows of the pool");
+      }
     }
 
     void scatter_row(const Request& req, const TensorNest& slice) {
@@ -1244,6 +1360,21 @@ class DynamicBatcher {
         std::memcpy(req.leaf_ptr(i), c.data_ptr(), layout.leaves[i].row_bytes);
         ++i;
       });
+      if (req.mailbox->has_state_rows()) {
+        // Into the half nobody reads (check_row_slice vouches for the
+        // shapes); complete_rows() makes it the current one.
+        const StateBlock& blk = *req.mailbox->state_block;
+        float* out = req.mailbox->state_out(req.env_index);
+        const int64_t n = blk.L * blk.H;
+        int64_t k = 0;
+        for (const auto& leaf : slice.vector()[1].vector()) {
+          const torch::Tensor& t = leaf.leaf();
+          torch::Tensor c = (t.is_cuda() ? t.cpu() : t).contiguous();
+          std::memcpy(out + k * n, c.data_ptr<float>(), n * sizeof(float));
+          ++k;
+        }
+        return;
+      }
       req.mailbox->state[req.env_index] = slice.vector()[1];
     }
 
@@ -1321,6 +1452,12 @@ class DynamicBatcher {
     device_gather_batches_.fetch_add(1, std::memory_order_relaxed);
   }
 
+  // Those of them that were recurrent: states read from and written to the
+  // pool's state rows by the LSTM serve kernels.
+  void count_state_row_batch() {
+    state_row_batches_.fetch_add(1, std::memory_order_relaxed);
+  }
+
   TensorNest compute(TensorNest inputs) {
     const int64_t t0 = now_us();
     std::future<TensorNest> future = compute_async(std::move(inputs));
@@ -1368,6 +1505,7 @@ class DynamicBatcher {
     out["serve_row_batches"] = (double)row_batches_.load();
     out["serve_device_gather_batches"] =
         (double)device_gather_batches_.load();
+    out["serve_state_row_batches"] = (double)state_row_batches_.load();
     out["computes"] = roundtrip_stats_.n.load();
     out["batches"] = batch_size_stats_.n.load();
     if (roundtrip_stats_.n > 0) {
@@ -1394,6 +1532,7 @@ class DynamicBatcher {
     serve_counters_.reset();
     row_batches_.store(0, std::memory_order_relaxed);
     device_gather_batches_.store(0, std::memory_order_relaxed);
+    state_row_batches_.store(0, std::memory_order_relaxed);
   }
 
  private:
@@ -1410,6 +1549,7 @@ class DynamicBatcher {
   CpuStageCounters serve_counters_;
   std::atomic<int64_t> row_batches_{0};
   std::atomic<int64_t> device_gather_batches_{0};
+  std::atomic<int64_t> state_row_batches_{0};
 };
 
 }  // namespace tbruntime

@@ -1,5 +1,5 @@
 // Declarations for runtime_kernels.hip (gather_obs, fused_heads_sample,
-// unpack_rollouts, gather_rows).
+// unpack_rollouts, gather_rows, lstm_serve_layer).
 #pragma once
 
 #include <torch/extension.h>
@@ -35,6 +35,76 @@ void fused_heads_sample_out(const torch::Tensor& x, const torch::Tensor& rew,
                             const torch::Tensor& base_b, int64_t b,
                             bool greedy, int64_t seed, int64_t* out_action,
                             float* out_logits, float* out_baseline);
+
+// The heads kernel over raw pointers. `core` is [>= b, D] f32 on the device;
+// with `rew` ([>= b] f32) the heads see [core, rew] (length D + 1), with
+// rew == nullptr the core alone (the recurrent tail: the last LSTM layer's
+// h). Same sampling code either way.
+void launch_heads_sample(const float* core, const float* rew, int64_t D,
+                         const torch::Tensor& policy_w,
+                         const torch::Tensor& policy_b,
+                         const torch::Tensor& base_w,
+                         const torch::Tensor& base_b, int64_t b, bool greedy,
+                         int64_t seed, int64_t* out_action, float* out_logits,
+                         float* out_baseline);
+
+// One LSTM layer's weights as lstm_serve_layer_kernel reads them (layout in
+// the kernel comment): w [4, Hn, Kp] bf16, bias [4, Hn] f32 = b_ih + b_hh.
+struct LstmLayerPack {
+  torch::Tensor w, bias;
+  int64_t I = 0, H = 0, Ip = 0, Kp = 0, Hn = 0;
+};
+// Packs with ATen ops on the current stream (a handful of launches and two
+// allocations: once per weight version, not per batch).
+LstmLayerPack pack_lstm_layer(const torch::Tensor& w_ih,
+                              const torch::Tensor& w_hh,
+                              const torch::Tensor& b_ih,
+                              const torch::Tensor& b_hh);
+
+// Does a layer with input length I and hidden size H fit the layer kernel's
+// LDS tile (16 rows of Ip + Hk bf16 plus 16 KB of partial sums in 64 KB:
+// I + H up to about 1,500)? The runner declines the recurrent row path for a
+// model that does not.
+bool lstm_serve_layer_fits(int64_t I, int64_t H);
+
+// The LSTM serve step's kernels (comments in the .hip), each one launch on
+// the current stream. The tables hold `b` pointers each in pinned host
+// memory and are filled by build_state_table() (row_gather.h), which checked
+// them; a wrong one is a GPU fault. Tables, state block and rows stay
+// unchanged until the stream has run the kernels.
+//
+// Stage: request r's previous state (n_floats = 2 L H floats, zeros for a
+// done row) from the pinned state rows into row r of `staged` (device,
+// [>= b, n_floats]).
+void launch_lstm_stage_state(const float* const* state_in,
+                             const uint8_t* const* done_src, int64_t b,
+                             int64_t n_floats, float* staged);
+// One layer. `in` is [>= b, in_stride] f32 on the device; for layer 0, `rew`
+// ([>= b]) is appended as the input's last element, for the other layers it
+// is nullptr. h_out is [>= b, H] on the device.
+void launch_lstm_serve_layer(float* const* state_out, const float* staged,
+                             const float* in, int64_t in_stride,
+                             const float* rew, const LstmLayerPack& pack,
+                             int64_t b, int64_t layer, int64_t L,
+                             float* h_out);
+
+// Test surface: every layer kernel and the heads on caller-made tensors. x
+// [n, D] and rew [n] f32 on the GPU (n >= b), lstm_weights four tensors per
+// layer (w_ih, w_hh, b_ih, b_hh) on the GPU. The state lives in
+// `state_block`, a pinned f32 CPU tensor: request r reads 2*L*H floats (h
+// [L, H], then c) at byte offset in_offsets[r] and writes as many at
+// out_offsets[r]; its done byte is at done_offsets[r] of the pinned uint8
+// `done_slab`. All offsets go through build_state_table() (IndexError /
+// ValueError) before anything is launched. Returns pinned (action [cap],
+// logits [cap, A], baseline [cap]) and then one device [cap, H] h per
+// layer, all pre-filled with -7 so that untouched rows show.
+std::vector<torch::Tensor> lstm_serve_step(
+    torch::Tensor x, torch::Tensor rew, std::vector<torch::Tensor> lstm_weights,
+    torch::Tensor policy_w, torch::Tensor policy_b, torch::Tensor base_w,
+    torch::Tensor base_b, torch::Tensor state_block,
+    std::vector<int64_t> in_offsets, std::vector<int64_t> out_offsets,
+    torch::Tensor done_slab, std::vector<int64_t> done_offsets, int64_t cap,
+    bool greedy, int64_t seed);
 
 // Rollout unpack (layout in rollout_gather.h): one launch on the current
 // stream; staging and every column's dst are device memory, staging holds

@@ -22,6 +22,13 @@
 // pinned table of row addresses (row_gather.h) and copies frames and clamped
 // rewards over the host link into the serve thread's device staging, so no
 // frame is copied on the host at all.
+//
+// lstm_serve_layer: the recurrent tail of a row batch. One bf16 MFMA kernel
+// per LSTM layer computes the gates and the cell update for the whole batch,
+// reading each request's (h, c) from the pool's pinned state rows and
+// writing the new state back there; the heads kernel then takes the last
+// layer's h as its core. Replaces ~40 ATen launches and the state's D2H
+// copies per batch of a two-layer core.
 
 #include <ATen/cuda/CUDAContext.h>
 #include <c10/cuda/CUDAGuard.h>
@@ -71,14 +78,16 @@ __global__ void gather_obs_kernel(
   }
 }
 
-// One workgroup per sample; the core vector ([x, rew], length D+1) is
-// staged in LDS, then each wave computes head dot products.
+// One workgroup per sample; the core vector is staged in LDS, then each wave
+// computes head dot products. The core is [x, rew] (length D+1, the
+// stateless model) or, with rew == nullptr, x alone (length D: the last
+// LSTM layer's h of the recurrent tail).
 __global__ __launch_bounds__(256) void heads_sample_kernel(
-    const float* __restrict__ x,         // [bp, D] fc output (post-relu)
-    const float* __restrict__ rew,       // [bp, 1]
-    const float* __restrict__ policy_w,  // [A, D+1]
+    const float* __restrict__ x,         // [bp, D] fc output (post-relu) or h
+    const float* __restrict__ rew,       // [bp, 1] or nullptr
+    const float* __restrict__ policy_w,  // [A, Dc]
     const float* __restrict__ policy_b,  // [A]
-    const float* __restrict__ base_w,    // [1, D+1]
+    const float* __restrict__ base_w,    // [1, Dc]
     const float* __restrict__ base_b,    // [1]
     int b, int D, int A, uint64_t seed, int greedy,
     int64_t* __restrict__ out_action,  // host pinned [b]
@@ -86,12 +95,12 @@ __global__ __launch_bounds__(256) void heads_sample_kernel(
     float* __restrict__ out_base) {    // host pinned [b]
   const int s = blockIdx.x;
   if (s >= b) return;
-  extern __shared__ float s_core[];  // [D+1]
-  const int Dc = D + 1;
+  extern __shared__ float s_core[];  // [Dc]
+  const int Dc = rew != nullptr ? D + 1 : D;
   for (int i = threadIdx.x; i < D; i += blockDim.x) {
     s_core[i] = x[(int64_t)s * D + i];
   }
-  if (threadIdx.x == 0) s_core[D] = rew[s];
+  if (rew != nullptr && threadIdx.x == 0) s_core[D] = rew[s];
   __syncthreads();
 
   // One lane group per output row (A logits + 1 baseline): wave-strided
@@ -313,6 +322,184 @@ __global__ __launch_bounds__(kGatherRowsThreads) void gather_rows_kernel(
     const float v = __builtin_nontemporal_load(rew_src[r]);
     out_rew[r] = v < -1.f ? -1.f : (v > 1.f ? 1.f : v);
   }
+}
+
+// lstm_serve_layer: one LSTM layer, one time step, for an inference batch
+// whose recurrent state lives in pinned host memory (the pool's state rows).
+// For request r and hidden unit j
+//   gates = W_ih in_r + W_hh (nd_r h_prev_r) + b_ih + b_hh      (i, f, g, o)
+//   c'    = sigmoid(f) (nd_r c_prev_r) + sigmoid(i) tanh(g)
+//   h'    = sigmoid(o) tanh(c')
+// as a bf16 MFMA GEMM (v_mfma_f32_16x16x32_bf16, f32 accumulation) with
+// M = requests, N = 4 gates x Hn, K = Ip + Hk: in_r and the masked h_prev_r
+// are rounded to bf16 into one LDS row of length Kp = Ip + Hk, the packed
+// weights [4, Hn, Kp] bf16 hold W_ih in columns [0, I) and W_hh in columns
+// [Ip, Ip + H), zero elsewhere (Ip, Hk: I, H rounded up to 32; Hn: H rounded
+// up to 16), so odd sizes such as 513 cost a padded k-step and masked
+// stores, not a special case. The cell path and the stored state are f32.
+//
+// A workgroup owns 16 requests x 16 hidden units with all four gate rows of
+// those units, so the cell update needs no second pass: grid (Hn / 16,
+// ceil(b / 16)), e.g. 33 x 8 = 264 workgroups for H = 513 at b = 128. Its
+// four waves split K (wave w takes k-steps w, w + 4, ...: the loop is bound
+// by the latency of streaming the weights from L2, and four short loops
+// hide more of it than one long one), each with one A fragment from LDS
+// and four B fragments (one per gate) straight from global memory per
+// k-step, no barrier in the loop. The partial sums meet in LDS, then thread
+// t finishes request t / 16, unit t % 16.
+//
+// The previous state comes from `staged`, device memory that
+// lstm_stage_state_kernel (below) filled from the pinned state rows once per
+// batch, with a done row's state already zeroed. The first version read
+// h_prev over the host link in every workgroup, i.e. Hn / 16 = 33 times per
+// request and layer; those workgroups sat on the CUs (and on 51 KB of LDS
+// each) waiting for the link, and `bench.py --use_lstm` fell from 89k to 65k
+// SPS (profiles/PROFILE_r7.md). h' and c' are written to pinned host memory
+// through the table of build_state_table() (row_gather.h), which has checked
+// every address and that no out range overlaps an in range, with ordinary
+// stores. h' also goes to `h_out` (device), the next layer's or the heads'
+// input. Only requests [0, b) are touched: the rows that pad the last
+// 16-row tile are zero in LDS and never dereference the table, nor are they
+// stored.
+constexpr int kLstmThreads = 256;
+constexpr int kLstmTile = 16;  // requests and hidden units per workgroup
+constexpr int kLstmRowPad = 8;  // bf16 elements between LDS rows
+
+using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
+using f32x4 = __attribute__((ext_vector_type(4))) float;
+
+__device__ __forceinline__ float sigmoidf_(float v) {
+  return 1.f / (1.f + __expf(-v));
+}
+
+// The batch's previous state, read ONCE from the pinned state rows: request
+// r's 2 L H floats (h [L, H], then c) go to row r of `staged` (device), or
+// zeros if its row's done byte is set (selected, not multiplied: a done
+// row's old state is not read at all). One workgroup per request; only
+// requests [0, b) are touched.
+__global__ __launch_bounds__(256) void lstm_stage_state_kernel(
+    const float* const* __restrict__ state_in,    // host pinned [b]
+    const uint8_t* const* __restrict__ done_src,  // host pinned [b]
+    int n_floats,
+    float* __restrict__ staged) {  // device [>= b, n_floats]
+  const int r = blockIdx.x;
+  const bool keep = *done_src[r] == 0;
+  const float* src = state_in[r];
+  float* dst = staged + (int64_t)r * n_floats;
+  for (int i = threadIdx.x; i < n_floats; i += 256) {
+    dst[i] = keep ? __builtin_nontemporal_load(src + i) : 0.f;
+  }
+}
+
+__global__ __launch_bounds__(kLstmThreads) void lstm_serve_layer_kernel(
+    float* const* __restrict__ state_out,  // host pinned [b]
+    const float* __restrict__ staged,      // device [>= b, 2 L H], masked
+    const float* __restrict__ in,    // device [>= b, in_stride]
+    const float* __restrict__ rew,   // device [>= b] or nullptr (layers > 0)
+    const __bf16* __restrict__ W,    // [4 * Hn, Kp]
+    const float* __restrict__ bias,  // [4 * Hn], b_ih + b_hh
+    int b, int layer, int L, int H, int I, int in_stride, int Ip, int Kp,
+    int Hn,
+    float* __restrict__ h_out) {  // device [>= b, H]
+  extern __shared__ __attribute__((aligned(16))) char lstm_smem[];
+  const int lda = Kp + kLstmRowPad;
+  __bf16* A = reinterpret_cast<__bf16*>(lstm_smem);
+  float* red = reinterpret_cast<float*>(lstm_smem + kLstmTile * lda * 2);
+  __shared__ float* s_out[kLstmTile];
+
+  const int tid = threadIdx.x;
+  const int u0 = blockIdx.x * kLstmTile;
+  const int m0 = blockIdx.y * kLstmTile;
+  if (tid < kLstmTile) {
+    const int r = m0 + tid;
+    s_out[tid] = r < b ? state_out[r] : nullptr;
+  }
+
+  // Stage [in_r, nd_r h_prev_r] as bf16: 16 lanes per request.
+  const int row = tid >> 4;
+  const int q = tid & 15;
+  const int r = m0 + row;
+  const bool valid = r < b;
+  const float* prev = staged + (int64_t)(valid ? r : 0) * 2 * L * H;
+  {
+    __bf16* a = A + row * lda;
+    const float* xin = in + (int64_t)(valid ? r : 0) * in_stride;
+    const int nx = rew != nullptr ? I - 1 : I;
+    for (int k = q; k < Ip; k += 16) {
+      float v = 0.f;
+      if (valid) {
+        if (k < nx) {
+          v = xin[k];
+        } else if (k < I) {
+          v = rew[r];
+        }
+      }
+      a[k] = (__bf16)v;
+    }
+    const float* hp = prev + (int64_t)layer * H;
+    for (int j = q; j < Kp - Ip; j += 16) {
+      a[Ip + j] = (__bf16)((valid && j < H) ? hp[j] : 0.f);
+    }
+  }
+  __syncthreads();
+
+  const int wave = tid >> 6;
+  const int lane = tid & 63;
+  const int ln = lane & 15;
+  const int lg = lane >> 4;
+  f32x4 acc[4];
+#pragma unroll
+  for (int g = 0; g < 4; ++g) acc[g] = {0.f, 0.f, 0.f, 0.f};
+  // A[m = ln][k = 8 lg + j] from LDS, B[k = 8 lg + j][n = ln] from the
+  // packed weights, which hold unit n's row k-contiguous.
+  const __bf16* al = A + ln * lda + lg * 8;
+  const __bf16* wl = W + (int64_t)(u0 + ln) * Kp + lg * 8;
+  const int64_t gate_stride = (int64_t)Hn * Kp;
+  const int ksteps = Kp >> 5;
+  for (int ks = wave; ks < ksteps; ks += kLstmThreads / 64) {
+    const bf16x8 a = *reinterpret_cast<const bf16x8*>(al + ks * 32);
+    bf16x8 w[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      w[g] = *reinterpret_cast<const bf16x8*>(wl + g * gate_stride + ks * 32);
+    }
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, w[g], acc[g], 0, 0, 0);
+    }
+  }
+  // C: column (unit) = lane & 15, row (request) = 4 (lane >> 4) + register.
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      red[((wave * 4 + g) * kLstmTile + lg * 4 + i) * kLstmTile + ln] =
+          acc[g][i];
+    }
+  }
+  __syncthreads();
+
+  const int j = u0 + q;
+  if (!valid || j >= H) return;
+  float gates[4];
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    float v = bias[g * Hn + j];
+#pragma unroll
+    for (int w = 0; w < kLstmThreads / 64; ++w) {
+      v += red[((w * 4 + g) * kLstmTile + row) * kLstmTile + q];
+    }
+    gates[g] = v;
+  }
+  const int64_t lh = (int64_t)layer * H + j;
+  const float c_prev = prev[(int64_t)L * H + lh];
+  const float c_new =
+      sigmoidf_(gates[1]) * c_prev + sigmoidf_(gates[0]) * tanhf(gates[2]);
+  const float h_new = sigmoidf_(gates[3]) * tanhf(c_new);
+  float* out = s_out[row];
+  out[lh] = h_new;
+  out[(int64_t)L * H + lh] = c_new;
+  h_out[(int64_t)r * H + j] = h_new;
 }
 
 }  // namespace
@@ -545,20 +732,221 @@ void fused_heads_sample_out(const torch::Tensor& x, const torch::Tensor& rew,
                             bool greedy, int64_t seed, int64_t* out_action,
                             float* out_logits, float* out_baseline) {
   const int D = x.size(1);
-  const int A = policy_w.size(0);
-  TORCH_CHECK(A <= 64, "heads kernel supports up to 64 actions");
   TORCH_CHECK(policy_w.size(1) == D + 1 && base_w.size(1) == D + 1,
               "head weights must take [x, reward]");
   TORCH_CHECK(b >= 1 && x.size(0) >= b && rew.numel() >= b,
               "heads kernel: batch exceeds its inputs");
-  const size_t lds = (size_t)(D + 1) * sizeof(float);
+  launch_heads_sample(x.data_ptr<float>(), rew.data_ptr<float>(), D, policy_w,
+                      policy_b, base_w, base_b, b, greedy, seed, out_action,
+                      out_logits, out_baseline);
+}
+
+void launch_heads_sample(const float* core, const float* rew, int64_t D,
+                         const torch::Tensor& policy_w,
+                         const torch::Tensor& policy_b,
+                         const torch::Tensor& base_w,
+                         const torch::Tensor& base_b, int64_t b, bool greedy,
+                         int64_t seed, int64_t* out_action, float* out_logits,
+                         float* out_baseline) {
+  const int A = policy_w.size(0);
+  const int64_t Dc = rew != nullptr ? D + 1 : D;
+  TORCH_CHECK(A <= 64, "heads kernel supports up to 64 actions");
+  TORCH_CHECK(policy_w.size(1) == Dc && base_w.size(1) == Dc &&
+                  policy_w.is_contiguous() && base_w.is_contiguous(),
+              "head weights do not match the core's length");
+  TORCH_CHECK(b >= 1 && core != nullptr, "heads kernel: empty batch");
+  const size_t lds = (size_t)Dc * sizeof(float);
   hipLaunchKernelGGL(heads_sample_kernel, dim3((uint32_t)b), dim3(256), lds,
-                     at::cuda::getCurrentCUDAStream(), x.data_ptr<float>(),
-                     rew.data_ptr<float>(), policy_w.data_ptr<float>(),
-                     policy_b.data_ptr<float>(), base_w.data_ptr<float>(),
-                     base_b.data_ptr<float>(), (int)b, D, A,
-                     (uint64_t)seed, greedy ? 1 : 0, out_action, out_logits,
-                     out_baseline);
+                     at::cuda::getCurrentCUDAStream(), core, rew,
+                     policy_w.data_ptr<float>(), policy_b.data_ptr<float>(),
+                     base_w.data_ptr<float>(), base_b.data_ptr<float>(),
+                     (int)b, (int)D, A, (uint64_t)seed, greedy ? 1 : 0,
+                     out_action, out_logits, out_baseline);
+}
+
+// ---- LSTM serve step ------------------------------------------------------
+
+namespace {
+int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
+}  // namespace
+
+// LDS of one workgroup of lstm_serve_layer_kernel: the bf16 A tile and the
+// four waves' partial sums.
+static size_t lstm_layer_lds_bytes(int64_t Kp) {
+  return (size_t)kLstmTile * (size_t)(Kp + kLstmRowPad) * 2 +
+         (size_t)(kLstmThreads / 64) * 4 * kLstmTile * kLstmTile *
+             sizeof(float);
+}
+
+bool lstm_serve_layer_fits(int64_t I, int64_t H) {
+  if (I < 1 || H < 1) return false;
+  return lstm_layer_lds_bytes(round_up(I, 32) + round_up(H, 32)) <= 64 * 1024;
+}
+
+LstmLayerPack pack_lstm_layer(const torch::Tensor& w_ih,
+                              const torch::Tensor& w_hh,
+                              const torch::Tensor& b_ih,
+                              const torch::Tensor& b_hh) {
+  TORCH_CHECK(w_ih.is_cuda() && w_ih.dim() == 2 && w_hh.dim() == 2 &&
+                  w_ih.scalar_type() == torch::kFloat32 &&
+                  w_hh.scalar_type() == torch::kFloat32,
+              "lstm pack: f32 GPU weight matrices expected");
+  LstmLayerPack p;
+  p.H = w_hh.size(1);
+  p.I = w_ih.size(1);
+  TORCH_CHECK(w_ih.size(0) == 4 * p.H && w_hh.size(0) == 4 * p.H &&
+                  b_ih.numel() == 4 * p.H && b_hh.numel() == 4 * p.H,
+              "lstm pack: weights disagree on the hidden size");
+  p.Ip = round_up(p.I, 32);
+  p.Kp = p.Ip + round_up(p.H, 32);
+  p.Hn = round_up(p.H, kLstmTile);
+  auto bf = w_ih.options().dtype(torch::kBFloat16);
+  p.w = torch::zeros({4, p.Hn, p.Kp}, bf);
+  p.w.narrow(1, 0, p.H).narrow(2, 0, p.I).copy_(w_ih.reshape({4, p.H, p.I}));
+  p.w.narrow(1, 0, p.H).narrow(2, p.Ip, p.H).copy_(w_hh.reshape({4, p.H, p.H}));
+  p.bias = torch::zeros({4, p.Hn}, w_ih.options());
+  p.bias.narrow(1, 0, p.H).copy_((b_ih + b_hh).reshape({4, p.H}));
+  return p;
+}
+
+void launch_lstm_stage_state(const float* const* state_in,
+                             const uint8_t* const* done_src, int64_t b,
+                             int64_t n_floats, float* staged) {
+  TORCH_CHECK(b >= 1 && n_floats >= 1 && n_floats < (int64_t(1) << 31),
+              "lstm stage: bad batch or state size");
+  TORCH_CHECK(state_in != nullptr && done_src != nullptr && staged != nullptr,
+              "lstm stage: null argument");
+  hipLaunchKernelGGL(lstm_stage_state_kernel, dim3((uint32_t)b), dim3(256), 0,
+                     at::cuda::getCurrentCUDAStream(), state_in, done_src,
+                     (int)n_floats, staged);
+  const hipError_t err = hipGetLastError();
+  TORCH_CHECK(err == hipSuccess, "lstm_stage_state launch: ",
+              hipGetErrorString(err));
+}
+
+void launch_lstm_serve_layer(float* const* state_out, const float* staged,
+                             const float* in, int64_t in_stride,
+                             const float* rew, const LstmLayerPack& p,
+                             int64_t b, int64_t layer, int64_t L,
+                             float* h_out) {
+  TORCH_CHECK(b >= 1 && layer >= 0 && layer < L, "lstm serve: bad batch/layer");
+  TORCH_CHECK(state_out != nullptr && staged != nullptr && in != nullptr &&
+                  h_out != nullptr,
+              "lstm serve: null argument");
+  TORCH_CHECK(p.w.defined() && p.w.is_contiguous() &&
+                  p.w.numel() == 4 * p.Hn * p.Kp && p.Kp % 32 == 0 &&
+                  p.Ip % 32 == 0 && p.Hn % kLstmTile == 0 && p.I <= p.Ip &&
+                  p.Ip + p.H <= p.Kp && p.H <= p.Hn &&
+                  p.bias.numel() == 4 * p.Hn,
+              "lstm serve: inconsistent weight pack");
+  TORCH_CHECK(in_stride >= (rew != nullptr ? p.I - 1 : p.I),
+              "lstm serve: input rows shorter than the layer's input");
+  const int64_t mtiles = (b + kLstmTile - 1) / kLstmTile;
+  TORCH_CHECK(mtiles <= 65535, "lstm serve: batch too large");
+  const size_t lds = lstm_layer_lds_bytes(p.Kp);
+  TORCH_CHECK(lds <= 64 * 1024, "lstm serve: layer too wide for one LDS tile");
+  hipLaunchKernelGGL(
+      lstm_serve_layer_kernel, dim3((uint32_t)(p.Hn / kLstmTile),
+                                    (uint32_t)mtiles),
+      dim3(kLstmThreads), lds, at::cuda::getCurrentCUDAStream(), state_out,
+      staged, in, rew,
+      reinterpret_cast<const __bf16*>(p.w.data_ptr()), p.bias.data_ptr<float>(),
+      (int)b, (int)layer, (int)L, (int)p.H, (int)p.I, (int)in_stride,
+      (int)p.Ip, (int)p.Kp, (int)p.Hn, h_out);
+  const hipError_t err = hipGetLastError();
+  TORCH_CHECK(err == hipSuccess, "lstm_serve_layer launch: ",
+              hipGetErrorString(err));
+}
+
+std::vector<torch::Tensor> lstm_serve_step(
+    torch::Tensor x, torch::Tensor rew, std::vector<torch::Tensor> lstm_weights,
+    torch::Tensor policy_w, torch::Tensor policy_b, torch::Tensor base_w,
+    torch::Tensor base_b, torch::Tensor state_block,
+    std::vector<int64_t> in_offsets, std::vector<int64_t> out_offsets,
+    torch::Tensor done_slab, std::vector<int64_t> done_offsets, int64_t cap,
+    bool greedy, int64_t seed) {
+  const int64_t b = (int64_t)in_offsets.size();
+  TORCH_CHECK(state_block.device().is_cpu() &&
+                  state_block.scalar_type() == torch::kFloat32 &&
+                  state_block.is_contiguous() && state_block.is_pinned(),
+              "lstm_serve_step: state block must be a contiguous pinned "
+              "float32 tensor");
+  TORCH_CHECK(done_slab.device().is_cpu() &&
+                  done_slab.scalar_type() == torch::kUInt8 &&
+                  done_slab.is_contiguous() && done_slab.is_pinned(),
+              "lstm_serve_step: done slab must be a contiguous pinned uint8 "
+              "tensor");
+  TORCH_CHECK(b >= 1 && out_offsets.size() == in_offsets.size() &&
+                  done_offsets.size() == in_offsets.size() && cap >= b,
+              "lstm_serve_step: need 1 <= b <= cap offsets of each kind");
+  TORCH_CHECK(!lstm_weights.empty() && lstm_weights.size() % 4 == 0,
+              "lstm_serve_step: four weight tensors per layer");
+  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.is_contiguous() &&
+                  x.scalar_type() == torch::kFloat32 && x.size(0) >= b &&
+                  rew.is_cuda() && rew.is_contiguous() &&
+                  rew.scalar_type() == torch::kFloat32 && rew.numel() >= b,
+              "lstm_serve_step: x [n, D] and rew [n] f32 on the GPU, n >= b");
+  at::cuda::CUDAGuard device_guard(x.device());
+  const int64_t L = (int64_t)lstm_weights.size() / 4;
+  TORCH_CHECK(lstm_weights[1].dim() == 2, "lstm_serve_step: w_hh is [4H, H]");
+  const int64_t H = lstm_weights[1].size(1);
+  // The one writer of addresses the kernels follow; it checks all of them,
+  // before anything is launched.
+  auto table = torch::empty({3 * b}, torch::TensorOptions()
+                                         .dtype(torch::kInt64)
+                                         .pinned_memory(true));
+  int64_t* t = table.data_ptr<int64_t>();
+  auto** in_tab = reinterpret_cast<const float**>(t);
+  auto** out_tab = reinterpret_cast<float**>(t + b);
+  auto** done_tab = reinterpret_cast<const uint8_t**>(t + 2 * b);
+  const auto* sbase = reinterpret_cast<const uint8_t*>(state_block.data_ptr());
+  const uint8_t* dbase = done_slab.data_ptr<uint8_t>();
+  std::vector<uintptr_t> scratch;
+  build_state_table(
+      b, [&](int64_t r) { return sbase + in_offsets[r]; },
+      [&](int64_t r) { return sbase + out_offsets[r]; },
+      [&](int64_t r) { return dbase + done_offsets[r]; }, 2 * L * H, sbase,
+      state_block.numel() * 4, dbase, done_slab.numel(), scratch, in_tab,
+      out_tab, done_tab);
+  std::vector<LstmLayerPack> packs;
+  for (int64_t l = 0; l < L; ++l) {
+    packs.push_back(pack_lstm_layer(lstm_weights[4 * l], lstm_weights[4 * l + 1],
+                                    lstm_weights[4 * l + 2],
+                                    lstm_weights[4 * l + 3]));
+    TORCH_CHECK(packs[l].H == H &&
+                    packs[l].I == (l == 0 ? x.size(1) + 1 : H),
+                "lstm_serve_step: layer ", l, " does not fit its input");
+  }
+  auto dopts = torch::TensorOptions().device(x.device());
+  auto hopts = torch::TensorOptions().pinned_memory(true);
+  const int64_t A = policy_w.size(0);
+  std::vector<torch::Tensor> hs;
+  for (int64_t l = 0; l < L; ++l) {
+    hs.push_back(torch::full({cap, H}, -7.0f, dopts.dtype(torch::kFloat32)));
+  }
+  auto action = torch::full({cap}, -7, hopts.dtype(torch::kInt64));
+  auto logits = torch::full({cap, A}, -7.0f, hopts.dtype(torch::kFloat32));
+  auto baseline = torch::full({cap}, -7.0f, hopts.dtype(torch::kFloat32));
+  auto staged = torch::empty({cap, 2 * L * H}, dopts.dtype(torch::kFloat32));
+  launch_lstm_stage_state(in_tab, done_tab, b, 2 * L * H,
+                          staged.data_ptr<float>());
+  for (int64_t l = 0; l < L; ++l) {
+    launch_lstm_serve_layer(
+        out_tab, staged.data_ptr<float>(),
+        l == 0 ? x.data_ptr<float>() : hs[l - 1].data_ptr<float>(),
+        l == 0 ? x.size(1) : H, l == 0 ? rew.data_ptr<float>() : nullptr,
+        packs[l], b, l, L, hs[l].data_ptr<float>());
+  }
+  launch_heads_sample(hs[L - 1].data_ptr<float>(), nullptr, H, policy_w,
+                      policy_b, base_w, base_b, b, greedy, seed,
+                      action.data_ptr<int64_t>(), logits.data_ptr<float>(),
+                      baseline.data_ptr<float>());
+  // Table, state block and done slab are read (and the block written) in
+  // place: nothing may go away or change under the kernels.
+  at::cuda::getCurrentCUDAStream().synchronize();
+  std::vector<torch::Tensor> out{action, logits, baseline};
+  for (auto& h : hs) out.push_back(h);
+  return out;
 }
 
 }  // namespace tbruntime
