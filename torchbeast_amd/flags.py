@@ -49,6 +49,9 @@ def add_optimizer_flags(parser: argparse.ArgumentParser):
                         help="RMSProp smoothing constant.")
     parser.add_argument("--momentum", default=0, type=float,
                         help="RMSProp momentum.")
+    parser.add_argument("--centered", action="store_true",
+                        help="Centered RMSProp: normalise by an estimate of "
+                             "the gradient's variance.")
     parser.add_argument("--epsilon", default=0.01, type=float,
                         help="RMSProp epsilon.")
     parser.add_argument("--grad_norm_clipping", default=40.0, type=float,

@@ -363,6 +363,7 @@ def train(flags):  # noqa: C901
         learner_model.parameters(),
         lr=flags.learning_rate,
         momentum=flags.momentum,
+        centered=getattr(flags, "centered", False),
         eps=flags.epsilon,
         alpha=flags.alpha,
     )

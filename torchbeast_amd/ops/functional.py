@@ -232,20 +232,39 @@ def lstm_unroll(core, x, notdone, state):
 
 
 def rmsprop_step(param, grad, square_avg, lr, alpha, eps, clip_norm=None,
-                 lr_tensor=None):
+                 lr_tensor=None, momentum_buf=None, grad_avg=None,
+                 momentum=0.0):
     """One RMSProp step over FLAT tensors, fused with global-norm clipping.
 
     All of param/grad/square_avg are 1-D views over the whole model (see
     parallel.flat_params). Returns the pre-clip gradient norm (0-dim tensor).
+
+    torch.optim.RMSprop semantics without weight decay: `momentum > 0`
+    needs `momentum_buf` (the velocity), and passing `grad_avg` selects the
+    centered variant. Both are flat float32 buffers of param's size,
+    updated in place. lr multiplies the velocity at the parameter update and
+    is never folded into the buffer.
     """
+    if momentum < 0:
+        raise ValueError("rmsprop: momentum must be >= 0, got %r" % momentum)
+    if momentum > 0 and momentum_buf is None:
+        raise RuntimeError(
+            "rmsprop: momentum=%r needs a momentum_buf" % momentum)
     ext = _ext_for(param, "rmsprop_step") if param.is_cuda else None
     if ext is not None:
         return ext.rmsprop_step(
             param, grad, square_avg, float(lr), float(alpha), float(eps),
             float(clip_norm) if clip_norm is not None else -1.0,
-            lr_tensor,
+            lr_tensor, momentum_buf, grad_avg, float(momentum),
         )
 
+    for name, buf in (("momentum_buf", momentum_buf), ("grad_avg", grad_avg)):
+        if buf is not None and (buf.dtype != param.dtype
+                                or buf.shape != param.shape):
+            raise RuntimeError(
+                "rmsprop: %s must match param (%s %s), got %s %s"
+                % (name, param.dtype, tuple(param.shape), buf.dtype,
+                   tuple(buf.shape)))
     if lr_tensor is not None:
         lr = float(lr_tensor.item())
     total_norm = grad.norm(2)
@@ -254,8 +273,19 @@ def rmsprop_step(param, grad, square_avg, lr, alpha, eps, clip_norm=None,
         if coef < 1:
             grad = grad.mul(coef)
     square_avg.mul_(alpha).addcmul_(grad, grad, value=1 - alpha)
-    avg = square_avg.sqrt().add_(eps)
-    param.addcdiv_(grad, avg, value=-lr)
+    if grad_avg is not None:
+        grad_avg.add_(grad - grad_avg, alpha=1 - alpha)
+        # The clamp is the one deviation from torch, which yields NaN when
+        # rounding makes square_avg - grad_avg^2 negative.
+        avg = torch.addcmul(square_avg, grad_avg, grad_avg, value=-1)
+        avg = avg.clamp_(min=0).sqrt_().add_(eps)
+    else:
+        avg = square_avg.sqrt().add_(eps)
+    if momentum > 0:
+        momentum_buf.mul_(momentum).addcdiv_(grad, avg)
+        param.add_(momentum_buf, alpha=-lr)
+    else:
+        param.addcdiv_(grad, avg, value=-lr)
     return total_norm
 
 

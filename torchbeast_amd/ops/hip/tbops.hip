@@ -271,11 +271,18 @@ __global__ void grad_norm_sq_kernel(const float* __restrict__ grad, int64_t n,
   if (threadIdx.x == 0) atomicAdd(out, red[0]);
 }
 
+// torch.optim.RMSprop semantics (no weight decay). MOMENTUM adds the velocity
+// buffer, CENTERED the running gradient mean; <false,false> touches neither
+// pointer and keeps the plain update's expression order.
+template <bool MOMENTUM, bool CENTERED>
 __global__ void rmsprop_update_kernel(
     float* __restrict__ param, const float* __restrict__ grad,
-    float* __restrict__ square_avg, int64_t n, float lr,
+    float* __restrict__ square_avg,
+    float* __restrict__ momentum_buf,  // MOMENTUM only
+    float* __restrict__ grad_avg,      // CENTERED only
+    int64_t n, float lr,
     const float* __restrict__ lr_ptr,  // overrides lr when non-null
-    float alpha, float eps, float clip_norm,
+    float alpha, float eps, float momentum, float clip_norm,
     const float* __restrict__ norm_sq, float* __restrict__ norm_out) {
   const float norm = sqrtf(*norm_sq);
   float coef = 1.f;
@@ -291,20 +298,79 @@ __global__ void rmsprop_update_kernel(
     float s = square_avg[i];
     s = alpha * s + (1.f - alpha) * g * g;
     square_avg[i] = s;
-    param[i] -= lr * g / (sqrtf(s) + eps);
+    if constexpr (!MOMENTUM && !CENTERED) {
+      param[i] -= lr * g / (sqrtf(s) + eps);
+    } else {
+      float avg;
+      if constexpr (CENTERED) {
+        float m = grad_avg[i];
+        m += (g - m) * (1.f - alpha);
+        grad_avg[i] = m;
+        // Rounding can push s - m*m below zero (torch yields NaN there).
+        avg = sqrtf(fmaxf(s - m * m, 0.f)) + eps;
+      } else {
+        avg = sqrtf(s) + eps;
+      }
+      if constexpr (MOMENTUM) {
+        // lr scales the velocity at the update, never inside the buffer.
+        const float b = momentum * momentum_buf[i] + g / avg;
+        momentum_buf[i] = b;
+        param[i] -= lr * b;
+      } else {
+        param[i] -= lr * g / avg;
+      }
+    }
   }
+}
+
+// A short or mistyped buffer would be an out-of-bounds access on the device;
+// reject it on the host instead.
+static void check_rmsprop_buffer(const torch::Tensor& t,
+                                 const torch::Tensor& param,
+                                 const char* name) {
+  TORCH_CHECK(t.scalar_type() == torch::kFloat32, "rmsprop: ", name,
+              " must be float32, got ", t.scalar_type());
+  TORCH_CHECK(t.is_contiguous(), "rmsprop: ", name, " must be contiguous");
+  TORCH_CHECK(t.device() == param.device(), "rmsprop: ", name, " is on ",
+              t.device(), ", param on ", param.device());
+  TORCH_CHECK(t.numel() == param.numel(), "rmsprop: ", name, " has ",
+              t.numel(), " elements, param has ", param.numel());
 }
 
 torch::Tensor rmsprop_step(torch::Tensor param, torch::Tensor grad,
                            torch::Tensor square_avg, double lr, double alpha,
                            double eps, double clip_norm,
-                           std::optional<torch::Tensor> lr_tensor = {}) {
-  TORCH_CHECK(param.is_cuda() && param.dim() == 1, "rmsprop: flat GPU tensor");
+                           std::optional<torch::Tensor> lr_tensor = {},
+                           std::optional<torch::Tensor> momentum_buf = {},
+                           std::optional<torch::Tensor> grad_avg = {},
+                           double momentum = 0.0) {
+  TORCH_CHECK(param.is_cuda() && param.dim() == 1 && param.numel() > 0,
+              "rmsprop: flat GPU tensor");
+  check_rmsprop_buffer(param, param, "param");
+  check_rmsprop_buffer(grad, param, "grad");
+  check_rmsprop_buffer(square_avg, param, "square_avg");
+  TORCH_CHECK(momentum >= 0.0, "rmsprop: momentum must be >= 0, got ",
+              momentum);
+  const bool use_momentum = momentum > 0.0;
+  const bool centered = grad_avg.has_value();
+  TORCH_CHECK(!use_momentum || momentum_buf.has_value(),
+              "rmsprop: momentum=", momentum, " needs a momentum_buf");
+  if (momentum_buf) check_rmsprop_buffer(*momentum_buf, param, "momentum_buf");
+  if (grad_avg) check_rmsprop_buffer(*grad_avg, param, "grad_avg");
+  if (lr_tensor) {
+    TORCH_CHECK(lr_tensor->scalar_type() == torch::kFloat32 &&
+                    lr_tensor->numel() >= 1 &&
+                    lr_tensor->device() == param.device(),
+                "rmsprop: lr_tensor must be a float32 tensor on param's "
+                "device");
+  }
   const int64_t n = param.numel();
   auto norm_sq = torch::zeros({1}, param.options());
   auto norm_out = torch::empty({}, param.options());
   const float* lr_p =
       lr_tensor ? lr_tensor->data_ptr<float>() : nullptr;
+  float* mom_p = use_momentum ? momentum_buf->data_ptr<float>() : nullptr;
+  float* gavg_p = centered ? grad_avg->data_ptr<float>() : nullptr;
 
   const int threads = 256;
   const int blocks = std::min<int64_t>(2048, ceil_div(n, threads));
@@ -312,11 +378,21 @@ torch::Tensor rmsprop_step(torch::Tensor param, torch::Tensor grad,
   hipLaunchKernelGGL(grad_norm_sq_kernel, dim3(blocks), dim3(threads), 0,
                      stream, grad.data_ptr<float>(), n,
                      norm_sq.data_ptr<float>());
-  hipLaunchKernelGGL(rmsprop_update_kernel, dim3(blocks), dim3(threads), 0,
-                     stream, param.data_ptr<float>(), grad.data_ptr<float>(),
-                     square_avg.data_ptr<float>(), n, (float)lr, lr_p,
-                     (float)alpha, (float)eps, (float)clip_norm,
-                     norm_sq.data_ptr<float>(), norm_out.data_ptr<float>());
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(threads), 0, stream,
+                       param.data_ptr<float>(), grad.data_ptr<float>(),
+                       square_avg.data_ptr<float>(), mom_p, gavg_p, n,
+                       (float)lr, lr_p, (float)alpha, (float)eps,
+                       (float)momentum, (float)clip_norm,
+                       norm_sq.data_ptr<float>(), norm_out.data_ptr<float>());
+  };
+  if (use_momentum) {
+    if (centered) launch(rmsprop_update_kernel<true, true>);
+    else launch(rmsprop_update_kernel<true, false>);
+  } else {
+    if (centered) launch(rmsprop_update_kernel<false, true>);
+    else launch(rmsprop_update_kernel<false, false>);
+  }
   return norm_out;
 }
 
@@ -549,7 +625,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rmsprop_step", &rmsprop_step, py::arg("param"), py::arg("grad"),
         py::arg("square_avg"), py::arg("lr"), py::arg("alpha"),
         py::arg("eps"), py::arg("clip_norm"),
-        py::arg("lr_tensor") = std::nullopt);
+        py::arg("lr_tensor") = std::nullopt,
+        py::arg("momentum_buf") = std::nullopt,
+        py::arg("grad_avg") = std::nullopt, py::arg("momentum") = 0.0);
   m.def("policy_sample", &policy_sample);
   m.def("lstm_unroll_fwd", &lstm_unroll_fwd);
   m.def("lstm_unroll_bwd", &lstm_unroll_bwd);

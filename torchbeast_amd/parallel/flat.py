@@ -62,22 +62,41 @@ class FusedRMSProp:
     and the reference's linear LR decay (ref hyperparams:
     monobeast.py:387-398). On GPU the whole step is one HIP kernel pass.
 
-    Matches torch.optim.RMSprop semantics for momentum=0, centered=False.
+    Matches torch.optim.RMSprop semantics for every momentum/centered
+    combination (weight_decay is not implemented), except that the centered
+    variance estimate is clamped at zero where torch would produce NaN. The
+    learning rate scales the momentum buffer at the parameter update, as in
+    torch, so the linear decay acts on the whole accumulated velocity.
     """
 
     def __init__(self, flat_param, flat_grad, lr, alpha=0.99, eps=0.01,
-                 clip_norm=None):
+                 clip_norm=None, momentum=0.0, centered=False):
+        if momentum < 0:
+            raise ValueError("momentum must be >= 0, got %r" % (momentum,))
         self.param = flat_param
         self.grad = flat_grad
         self.base_lr = lr
         self.alpha = alpha
         self.eps = eps
         self.clip_norm = clip_norm
+        self.momentum = float(momentum)
+        self.centered = bool(centered)
         self.square_avg = torch.zeros_like(flat_param)
+        # Allocated once, and only when used: the captured step holds their
+        # addresses.
+        self.momentum_buf = None
+        self.grad_avg = None
+        self._ensure_buffers()
         self.lr_factor = 1.0
         self.steps = 0
         self.last_grad_norm = None
         self.lr_dev = None  # device-resident lr (hipGraph capture mode)
+
+    def _ensure_buffers(self):
+        if self.momentum > 0 and self.momentum_buf is None:
+            self.momentum_buf = torch.zeros_like(self.param)
+        if self.centered and self.grad_avg is None:
+            self.grad_avg = torch.zeros_like(self.param)
 
     @property
     def lr(self):
@@ -108,11 +127,14 @@ class FusedRMSProp:
             self.eps,
             self.clip_norm,
             self.lr_dev,
+            self.momentum_buf if self.momentum > 0 else None,
+            self.grad_avg if self.centered else None,
+            self.momentum,
         )
         self.steps += 1
 
     def state_dict(self):
-        return {
+        state = {
             "square_avg": self.square_avg,
             "steps": self.steps,
             "lr_factor": self.lr_factor,
@@ -120,9 +142,27 @@ class FusedRMSProp:
             "alpha": self.alpha,
             "eps": self.eps,
             "clip_norm": self.clip_norm,
+            "momentum": self.momentum,
+            "centered": self.centered,
         }
+        if self.momentum_buf is not None:
+            state["momentum_buf"] = self.momentum_buf
+        if self.grad_avg is not None:
+            state["grad_avg"] = self.grad_avg
+        return state
 
     def load_state_dict(self, state):
+        # Checkpoints written before momentum/centered existed carry none of
+        # these keys: the constructor's values stay and the buffers start at
+        # zero, which is what torch does on a first step.
+        self.momentum = float(state.get("momentum", self.momentum))
+        self.centered = bool(state.get("centered", self.centered))
+        self._ensure_buffers()
+        for name in ("momentum_buf", "grad_avg"):
+            if name in state:
+                if getattr(self, name) is None:
+                    setattr(self, name, torch.zeros_like(self.param))
+                getattr(self, name).copy_(state[name])
         self.square_avg.copy_(state["square_avg"])
         self.steps = state["steps"]
         self.lr_factor = state["lr_factor"]

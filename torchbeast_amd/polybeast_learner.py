@@ -326,6 +326,10 @@ def learn(
                 side = torch.cuda.Stream()
                 side.wait_stream(torch.cuda.current_stream())
                 with torch.cuda.stream(side):
+                    # Known: these are real optimizer steps, so
+                    # the first batch is applied three times here and once
+                    # more by the first replay. With --momentum > 0 (or
+                    # --centered) they also land in momentum_buf/grad_avg.
                     for _ in range(3):
                         device_step(*static_in)
                 torch.cuda.current_stream().wait_stream(side)
@@ -458,11 +462,6 @@ def train(flags):  # noqa: C901
     with torch.no_grad():
         actor_flat.copy_(flat_param)
 
-    if getattr(flags, "momentum", 0):
-        raise ValueError(
-            "polybeast's fused RMSProp implements momentum=0 semantics only; "
-            "got --momentum %r (use monobeast for momentum>0)" % flags.momentum
-        )
     optimizer = tbflat.FusedRMSProp(
         flat_param,
         flat_grad,
@@ -470,6 +469,8 @@ def train(flags):  # noqa: C901
         alpha=flags.alpha,
         eps=flags.epsilon,
         clip_norm=flags.grad_norm_clipping,
+        momentum=getattr(flags, "momentum", 0.0),
+        centered=getattr(flags, "centered", False),
     )
     steps_per_update = flags.unroll_length * flags.batch_size * world_size
     scheduler = tbflat.LinearLR(optimizer, steps_per_update, flags.total_steps)
