@@ -39,6 +39,9 @@ def add_loss_flags(parser: argparse.ArgumentParser):
                         help="Discount factor.")
     parser.add_argument("--reward_clipping", default="abs_one",
                         choices=["abs_one", "none"], help="Reward clipping.")
+    parser.add_argument("--vtrace_lambda", default=1.0, type=float,
+                        help="V-trace trace decay in [0, 1]: "
+                             "c_t = lambda * min(1, rho_t).")
     return parser
 
 

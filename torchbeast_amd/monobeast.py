@@ -260,6 +260,7 @@ def learn(
             rewards=rewards,
             values=learner_outputs["baseline"],
             bootstrap_value=bootstrap_value,
+            lambda_=flags.vtrace_lambda,
         )
 
         pg_loss, baseline_loss, entropy_loss = tbops.fused_impala_loss(

@@ -6,6 +6,7 @@ The compiled extension (`torchbeast_amd.ops._tbops`, built from
 wraps them in `torch.autograd.Function`s and exposes:
 
 - `vtrace_from_logits(...)`         — fused V-trace (log-probs + clip + scan)
+- `vtrace_from_importance_weights(...)` — the same scan from given log_rhos
 - `fused_impala_loss(...)`          — all three losses + grads in one kernel
 - `lstm_unroll(...)`                — done-masked multi-layer LSTM over T
 - `rmsprop_step(...)`               — fused global-norm clip + RMSProp
@@ -81,5 +82,6 @@ from torchbeast_amd.ops.functional import (  # noqa: E402,F401
     lstm_unroll,
     policy_sample,
     rmsprop_step,
+    vtrace_from_importance_weights,
     vtrace_from_logits,
 )

@@ -32,8 +32,15 @@ def _ext_for(tensor, symbol):
 
 
 # ---------------------------------------------------------------------------
-# V-trace (fused): action log-probs + rho/c clip + reverse scan + advantages.
+# V-trace (fused): action log-probs + rho/c clip + reverse scan + advantages;
+# from_importance_weights is the same kernel design starting at log_rhos.
 # ---------------------------------------------------------------------------
+
+
+def _clip_or_inf(threshold):
+    """None means "do not clip": the kernels take +inf, and
+    fminf(rho, inf) is rho exactly."""
+    return float("inf") if threshold is None else float(threshold)
 
 
 def vtrace_from_logits(
@@ -46,9 +53,11 @@ def vtrace_from_logits(
     bootstrap_value,
     clip_rho_threshold=1.0,
     clip_pg_rho_threshold=1.0,
+    lambda_=1.0,
 ):
     from torchbeast_amd.core import vtrace as pyvtrace
 
+    lambda_ = pyvtrace.check_lambda(lambda_)
     ext = _ext_for(target_policy_logits, "vtrace_from_logits")
     if ext is None:
         # Eager path (also the oracle): delegate to the pure-PyTorch module.
@@ -63,6 +72,7 @@ def vtrace_from_logits(
             bootstrap_value,
             clip_rho_threshold,
             clip_pg_rho_threshold,
+            lambda_,
         )
         return pyvtrace.VTraceFromLogitsReturns(
             vs=core.vs,
@@ -81,8 +91,9 @@ def vtrace_from_logits(
             rewards.detach().float().contiguous(),
             values.detach().float().contiguous(),
             bootstrap_value.detach().float().contiguous(),
-            float(clip_rho_threshold),
-            float(clip_pg_rho_threshold),
+            _clip_or_inf(clip_rho_threshold),
+            _clip_or_inf(clip_pg_rho_threshold),
+            lambda_,
         )
     return pyvtrace.VTraceFromLogitsReturns(
         vs=vs,
@@ -91,6 +102,46 @@ def vtrace_from_logits(
         behavior_action_log_probs=blp,
         target_action_log_probs=tlp,
     )
+
+
+def vtrace_from_importance_weights(
+    log_rhos,
+    discounts,
+    rewards,
+    values,
+    bootstrap_value,
+    clip_rho_threshold=1.0,
+    clip_pg_rho_threshold=1.0,
+    lambda_=1.0,
+):
+    from torchbeast_amd.core import vtrace as pyvtrace
+
+    lambda_ = pyvtrace.check_lambda(lambda_)
+    ext = _ext_for(log_rhos, "vtrace_from_importance_weights")
+    if ext is None:
+        return pyvtrace.from_importance_weights_eager(
+            log_rhos,
+            discounts,
+            rewards,
+            values,
+            bootstrap_value,
+            clip_rho_threshold,
+            clip_pg_rho_threshold,
+            lambda_,
+        )
+
+    with torch.no_grad():
+        vs, pg_adv = ext.vtrace_from_importance_weights(
+            log_rhos.detach().float().contiguous(),
+            discounts.detach().float().contiguous(),
+            rewards.detach().float().contiguous(),
+            values.detach().float().contiguous(),
+            bootstrap_value.detach().float().contiguous(),
+            _clip_or_inf(clip_rho_threshold),
+            _clip_or_inf(clip_pg_rho_threshold),
+            lambda_,
+        )
+    return pyvtrace.VTraceReturns(vs=vs, pg_advantages=pg_adv)
 
 
 # ---------------------------------------------------------------------------

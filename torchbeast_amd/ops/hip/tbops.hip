@@ -22,7 +22,9 @@
 #include <hiprand/hiprand_kernel.h>
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
+#include <c10/cuda/CUDAGuard.h>
 
+#include <climits>
 #include <vector>
 
 #include "atari_trunk.h"
@@ -43,6 +45,70 @@ static inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b)
 // V-trace: log-probs + rho/c clip + reverse scan + pg advantages, one launch.
 // ---------------------------------------------------------------------------
 
+// The per-element arithmetic shared by vtrace_kernel (from logits) and
+// vtrace_iw_kernel (from log_rhos): both call these, so the two entry points
+// cannot drift. A clip threshold of +inf means "do not clip": fminf(rho, inf)
+// is rho exactly. c is clipped at 1 regardless, then scaled by lambda
+// (arXiv:1802.01561 Remark 2); lambda = 1 multiplies exactly.
+__device__ __forceinline__ void vtrace_clip(float log_rho, float clip_rho,
+                                            float lambda, float* crho,
+                                            float* c) {
+  const float rho = __expf(log_rho);
+  *crho = fminf(rho, clip_rho);
+  *c = lambda * fminf(rho, 1.f);
+}
+
+__device__ __forceinline__ float vtrace_delta(float crho, float r, float disc,
+                                              float v_next, float v) {
+  return crho * (r + disc * v_next - v);
+}
+
+__device__ __forceinline__ float vtrace_scan_step(float delta, float disc,
+                                                  float c, float acc) {
+  return delta + disc * c * acc;
+}
+
+__device__ __forceinline__ float vtrace_advantage(float log_rho, float clip_pg,
+                                                  float r, float disc,
+                                                  float vs_next, float v) {
+  const float rho = __expf(log_rho);
+  return fminf(rho, clip_pg) * (r + disc * vs_next - v);
+}
+
+// Phases 2 and 3 of both kernels, entered after phase 1 has filled s_cs and
+// s_delta: the reverse recurrence on one thread, then vs and pg_adv
+// thread-strided over T. log_rhos is read back from global memory (written
+// by this workgroup's phase 1 in vtrace_kernel, an input in vtrace_iw_kernel)
+// and exp'd again rather than kept in LDS.
+__device__ __forceinline__ void vtrace_scan_and_outputs(
+    const float* s_cs, const float* s_delta, float* s_vmv,
+    const float* log_rhos, const float* discounts, const float* rewards,
+    const float* values, const float* bootstrap, float clip_pg, int T, int B,
+    int b, float* vs, float* pg_adv) {
+  __syncthreads();
+
+  if (threadIdx.x == 0) {
+    // The inherently sequential reverse recurrence over T.
+    float acc = 0.f;
+    for (int t = T - 1; t >= 0; --t) {
+      acc = vtrace_scan_step(s_delta[t], discounts[(int64_t)t * B + b],
+                             s_cs[t], acc);
+      s_vmv[t] = acc;
+    }
+  }
+  __syncthreads();
+
+  for (int t = threadIdx.x; t < T; t += blockDim.x) {
+    const int64_t idx = (int64_t)t * B + b;
+    const float v = values[idx];
+    vs[idx] = s_vmv[t] + v;
+    const float vs_next =
+        (t + 1 < T) ? (s_vmv[t + 1] + values[idx + B]) : bootstrap[b];
+    pg_adv[idx] = vtrace_advantage(log_rhos[idx], clip_pg, rewards[idx],
+                                   discounts[idx], vs_next, v);
+  }
+}
+
 // One workgroup per batch column b. Dynamic LDS: [3*T] floats
 // (cs, deltas, vs_minus_v).
 __global__ void vtrace_kernel(
@@ -53,7 +119,7 @@ __global__ void vtrace_kernel(
     const float* __restrict__ rewards,          // [T,B]
     const float* __restrict__ values,           // [T,B]
     const float* __restrict__ bootstrap,        // [B]
-    float clip_rho, float clip_pg, int T, int B, int A,
+    float clip_rho, float clip_pg, float lambda, int T, int B, int A,
     float* __restrict__ vs,        // [T,B]
     float* __restrict__ pg_adv,    // [T,B]
     float* __restrict__ log_rhos,  // [T,B]
@@ -85,46 +151,117 @@ __global__ void vtrace_kernel(
     blp[idx] = b_lp;
     log_rhos[idx] = lr;
 
-    const float rho = __expf(lr);
-    const float crho = fminf(rho, clip_rho);
-    s_cs[t] = fminf(rho, 1.f);
+    float crho, c;
+    vtrace_clip(lr, clip_rho, lambda, &crho, &c);
+    s_cs[t] = c;
     const float v_next = (t + 1 < T) ? values[idx + B] : bootstrap[b];
-    s_delta[t] =
-        crho * (rewards[idx] + discounts[idx] * v_next - values[idx]);
+    s_delta[t] = vtrace_delta(crho, rewards[idx], discounts[idx], v_next,
+                              values[idx]);
   }
-  __syncthreads();
+  vtrace_scan_and_outputs(s_cs, s_delta, s_vmv, log_rhos, discounts, rewards,
+                          values, bootstrap, clip_pg, T, B, b, vs, pg_adv);
+}
 
-  if (threadIdx.x == 0) {
-    // The inherently sequential reverse recurrence over T.
-    float acc = 0.f;
-    for (int t = T - 1; t >= 0; --t) {
-      acc = s_delta[t] + discounts[(int64_t)t * B + b] * s_cs[t] * acc;
-      s_vmv[t] = acc;
-    }
-  }
-  __syncthreads();
+// vtrace_kernel without the log-prob phase: log_rhos is an input (any policy
+// head, not only one softmax). Same grid, LDS layout and arithmetic.
+__global__ void vtrace_iw_kernel(
+    const float* __restrict__ log_rhos,   // [T,B]
+    const float* __restrict__ discounts,  // [T,B]
+    const float* __restrict__ rewards,    // [T,B]
+    const float* __restrict__ values,     // [T,B]
+    const float* __restrict__ bootstrap,  // [B]
+    float clip_rho, float clip_pg, float lambda, int T, int B,
+    float* __restrict__ vs,        // [T,B]
+    float* __restrict__ pg_adv) {  // [T,B]
+  extern __shared__ float smem[];
+  float* s_cs = smem;           // [T]
+  float* s_delta = smem + T;    // [T]
+  float* s_vmv = smem + 2 * T;  // [T]
+
+  const int b = blockIdx.x;
 
   for (int t = threadIdx.x; t < T; t += blockDim.x) {
     const int64_t idx = (int64_t)t * B + b;
-    const float v = values[idx];
-    vs[idx] = s_vmv[t] + v;
-    const float vs_next =
-        (t + 1 < T) ? (s_vmv[t + 1] + values[idx + B]) : bootstrap[b];
-    const float rho = __expf(log_rhos[idx]);
-    pg_adv[idx] = fminf(rho, clip_pg) *
-                  (rewards[idx] + discounts[idx] * vs_next - v);
+    float crho, c;
+    vtrace_clip(log_rhos[idx], clip_rho, lambda, &crho, &c);
+    s_cs[t] = c;
+    const float v_next = (t + 1 < T) ? values[idx + B] : bootstrap[b];
+    s_delta[t] = vtrace_delta(crho, rewards[idx], discounts[idx], v_next,
+                              values[idx]);
   }
+  vtrace_scan_and_outputs(s_cs, s_delta, s_vmv, log_rhos, discounts, rewards,
+                          values, bootstrap, clip_pg, T, B, b, vs, pg_adv);
 }
 
+// A tensor of the wrong shape, dtype or device would be an out-of-bounds or
+// misread access on the device; reject it on the host instead. `first` is
+// the entry point's first tensor, which fixes the GPU and T, B (and A).
+static void check_vtrace_tensor(const torch::Tensor& t,
+                                const torch::Tensor& first,
+                                at::IntArrayRef shape, const char* name,
+                                bool integral = false) {
+  TORCH_CHECK(t.device() == first.device(), "vtrace: ", name, " is on ",
+              t.device(), ", expected ", first.device());
+  if (integral) {
+    TORCH_CHECK(at::isIntegralType(t.scalar_type(), /*includeBool=*/false),
+                "vtrace: ", name, " must be an integer tensor, got ",
+                t.scalar_type());
+  } else {
+    TORCH_CHECK(t.scalar_type() == torch::kFloat32, "vtrace: ", name,
+                " must be float32, got ", t.scalar_type());
+    TORCH_CHECK(t.is_contiguous(), "vtrace: ", name, " must be contiguous");
+  }
+  TORCH_CHECK(t.sizes() == shape, "vtrace: ", name, " has shape ", t.sizes(),
+              ", expected ", shape);
+}
+
+// Scalars and sizes common to both entry points. Returns the dynamic LDS
+// request, which has to fit the device's per-workgroup limit: the kernels
+// keep three [T] float rows in LDS.
+static size_t check_vtrace_launch(const torch::Tensor& first, int64_t T,
+                                  int64_t B, int64_t A, double lambda) {
+  TORCH_CHECK(T >= 1 && B >= 1 && A >= 1,
+              "vtrace: T, B and A must be >= 1, got T=", T, " B=", B,
+              " A=", A);
+  TORCH_CHECK(B <= INT_MAX && A <= INT_MAX, "vtrace: B=", B, " or A=", A,
+              " exceeds the kernel's 32-bit sizes");
+  TORCH_CHECK(lambda >= 0.0 && lambda <= 1.0,
+              "vtrace: lambda must be in [0, 1], got ", lambda);
+  const size_t limit =
+      at::cuda::getDeviceProperties(first.get_device())->sharedMemPerBlock;
+  TORCH_CHECK((uint64_t)T <= limit / (3 * sizeof(float)),
+              "vtrace: unroll length T=", T, " needs ", 3 * sizeof(float),
+              "*T bytes of LDS, the device allows ", limit,
+              " per workgroup (T <= ", limit / (3 * sizeof(float)), ")");
+  return 3 * (size_t)T * sizeof(float);
+}
+
+// Actions are not range-checked: that needs a device-side reduction and a
+// host sync, which the learner step (and hipGraph capture) cannot afford.
+// An action outside [0, A) reads a neighbouring logit or past the buffer.
 std::vector<torch::Tensor> vtrace_from_logits(
     torch::Tensor behavior_logits, torch::Tensor target_logits,
     torch::Tensor actions, torch::Tensor discounts, torch::Tensor rewards,
     torch::Tensor values, torch::Tensor bootstrap, double clip_rho,
-    double clip_pg) {
-  TORCH_CHECK(behavior_logits.is_cuda(), "vtrace: expected GPU tensors");
-  const int T = behavior_logits.size(0);
-  const int B = behavior_logits.size(1);
-  const int A = behavior_logits.size(2);
+    double clip_pg, double lambda = 1.0) {
+  TORCH_CHECK(behavior_logits.is_cuda() && behavior_logits.dim() == 3,
+              "vtrace: behavior_logits must be a [T,B,A] GPU tensor");
+  const int64_t T = behavior_logits.size(0);
+  const int64_t B = behavior_logits.size(1);
+  const int64_t A = behavior_logits.size(2);
+  check_vtrace_tensor(behavior_logits, behavior_logits, {T, B, A},
+                      "behavior_logits");
+  check_vtrace_tensor(target_logits, behavior_logits, {T, B, A},
+                      "target_logits");
+  check_vtrace_tensor(actions, behavior_logits, {T, B}, "actions",
+                      /*integral=*/true);
+  check_vtrace_tensor(discounts, behavior_logits, {T, B}, "discounts");
+  check_vtrace_tensor(rewards, behavior_logits, {T, B}, "rewards");
+  check_vtrace_tensor(values, behavior_logits, {T, B}, "values");
+  check_vtrace_tensor(bootstrap, behavior_logits, {B}, "bootstrap");
+  const size_t lds = check_vtrace_launch(behavior_logits, T, B, A, lambda);
+
+  const at::cuda::CUDAGuard device_guard(behavior_logits.device());
   auto opts = behavior_logits.options();
   auto vs = torch::empty({T, B}, opts);
   auto pg_adv = torch::empty({T, B}, opts);
@@ -134,7 +271,6 @@ std::vector<torch::Tensor> vtrace_from_logits(
   auto actions_i64 = actions.to(torch::kInt64).contiguous();
 
   const int threads = 256;
-  const size_t lds = 3 * (size_t)T * sizeof(float);
   hipLaunchKernelGGL(vtrace_kernel, dim3(B), dim3(threads), lds,
                      at::cuda::getCurrentCUDAStream(),
                      behavior_logits.data_ptr<float>(),
@@ -142,11 +278,44 @@ std::vector<torch::Tensor> vtrace_from_logits(
                      actions_i64.data_ptr<int64_t>(),
                      discounts.data_ptr<float>(), rewards.data_ptr<float>(),
                      values.data_ptr<float>(), bootstrap.data_ptr<float>(),
-                     (float)clip_rho, (float)clip_pg, T, B, A,
-                     vs.data_ptr<float>(), pg_adv.data_ptr<float>(),
-                     log_rhos.data_ptr<float>(), blp.data_ptr<float>(),
-                     tlp.data_ptr<float>());
+                     (float)clip_rho, (float)clip_pg, (float)lambda, (int)T,
+                     (int)B, (int)A, vs.data_ptr<float>(),
+                     pg_adv.data_ptr<float>(), log_rhos.data_ptr<float>(),
+                     blp.data_ptr<float>(), tlp.data_ptr<float>());
+  DEVCHECK(hipGetLastError());
   return {vs, pg_adv, log_rhos, blp, tlp};
+}
+
+std::vector<torch::Tensor> vtrace_from_importance_weights(
+    torch::Tensor log_rhos, torch::Tensor discounts, torch::Tensor rewards,
+    torch::Tensor values, torch::Tensor bootstrap, double clip_rho,
+    double clip_pg, double lambda = 1.0) {
+  TORCH_CHECK(log_rhos.is_cuda() && log_rhos.dim() == 2,
+              "vtrace: log_rhos must be a [T,B] GPU tensor");
+  const int64_t T = log_rhos.size(0);
+  const int64_t B = log_rhos.size(1);
+  check_vtrace_tensor(log_rhos, log_rhos, {T, B}, "log_rhos");
+  check_vtrace_tensor(discounts, log_rhos, {T, B}, "discounts");
+  check_vtrace_tensor(rewards, log_rhos, {T, B}, "rewards");
+  check_vtrace_tensor(values, log_rhos, {T, B}, "values");
+  check_vtrace_tensor(bootstrap, log_rhos, {B}, "bootstrap");
+  const size_t lds = check_vtrace_launch(log_rhos, T, B, /*A=*/1, lambda);
+
+  const at::cuda::CUDAGuard device_guard(log_rhos.device());
+  auto opts = log_rhos.options();
+  auto vs = torch::empty({T, B}, opts);
+  auto pg_adv = torch::empty({T, B}, opts);
+
+  const int threads = 256;
+  hipLaunchKernelGGL(vtrace_iw_kernel, dim3(B), dim3(threads), lds,
+                     at::cuda::getCurrentCUDAStream(),
+                     log_rhos.data_ptr<float>(), discounts.data_ptr<float>(),
+                     rewards.data_ptr<float>(), values.data_ptr<float>(),
+                     bootstrap.data_ptr<float>(), (float)clip_rho,
+                     (float)clip_pg, (float)lambda, (int)T, (int)B,
+                     vs.data_ptr<float>(), pg_adv.data_ptr<float>());
+  DEVCHECK(hipGetLastError());
+  return {vs, pg_adv};
 }
 
 // ---------------------------------------------------------------------------
@@ -620,7 +789,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mfma_gemm", &tbamd::mfma_gemm);
   m.def("mfma_gemm_probe", &tbamd::mfma_gemm_probe);
   m.def("mfma_gemm_v2", &tbamd::mfma_gemm_v2);
-  m.def("vtrace_from_logits", &vtrace_from_logits);
+  m.def("vtrace_from_logits", &vtrace_from_logits,
+        py::arg("behavior_logits"), py::arg("target_logits"),
+        py::arg("actions"), py::arg("discounts"), py::arg("rewards"),
+        py::arg("values"), py::arg("bootstrap"), py::arg("clip_rho"),
+        py::arg("clip_pg"), py::arg("lambda_") = 1.0);
+  m.def("vtrace_from_importance_weights", &vtrace_from_importance_weights,
+        py::arg("log_rhos"), py::arg("discounts"), py::arg("rewards"),
+        py::arg("values"), py::arg("bootstrap"), py::arg("clip_rho"),
+        py::arg("clip_pg"), py::arg("lambda_") = 1.0);
   m.def("fused_impala_loss_fwd", &fused_impala_loss_fwd);
   m.def("rmsprop_step", &rmsprop_step, py::arg("param"), py::arg("grad"),
         py::arg("square_avg"), py::arg("lr"), py::arg("alpha"),

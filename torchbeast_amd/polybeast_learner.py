@@ -262,6 +262,7 @@ def learn(
             rewards=clipped_rewards,
             values=learner_outputs.baseline,
             bootstrap_value=bootstrap_value,
+            lambda_=flags.vtrace_lambda,
         )
 
         pg_loss, baseline_loss, entropy_loss = tbops.fused_impala_loss(
