@@ -4,6 +4,9 @@ Every fused CDNA4 kernel is compared against the eager implementation that
 the CPU path uses (which is itself oracle-tested against NumPy in
 test_vtrace.py / test_losses.py / test_flat.py)."""
 
+import os
+import sys
+
 import pytest
 import torch
 
@@ -15,6 +18,11 @@ if torch.cuda.is_available():
     from torchbeast_amd.parallel import flat as tbflat
 else:  # pragma: no cover
     pytest.skip("requires ROCm GPU", allow_module_level=True)
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)),
+                                "helpers"))
+
+from lstm_oracle import lstm_mimic as _lstm_mimic  # noqa: E402
 
 
 def test_hip_extension_loaded():
@@ -111,41 +119,6 @@ def test_policy_sample_distribution_and_greedy():
 
     greedy = tbops.policy_sample(logits[:5], greedy=True)
     assert (greedy.cpu() == 0).all()
-
-
-def _bf(t):
-    return t.to(torch.bfloat16).float()
-
-
-def _lstm_mimic(core, x, notdone, state):
-    """Eager unroll that rounds the recurrent-matmul operands to bf16 where
-    the v4 kernel does (gates = precomp_fp32 + bf16(masked h) @ bf16(W_hh)^T,
-    fp32 cell path) — the precision-faithful oracle."""
-    L = core.num_layers
-    h, c = (s.clone() for s in state)
-    layer_in = x
-    for l in range(L):
-        w_ih = getattr(core, f"weight_ih_l{l}")
-        w_hh = getattr(core, f"weight_hh_l{l}")
-        bias = getattr(core, f"bias_ih_l{l}") + getattr(core, f"bias_hh_l{l}")
-        pre = layer_in @ w_ih.t() + bias
-        outs = []
-        hl, cl = h[l], c[l]
-        for t in range(x.shape[0]):
-            nd = notdone[t].view(-1, 1)
-            hm = nd * hl
-            cmt = nd * cl
-            gates = pre[t] + _bf(hm) @ _bf(w_hh).t()
-            gi, gf, gg, go = gates.chunk(4, dim=-1)
-            gi, gf, go = gi.sigmoid(), gf.sigmoid(), go.sigmoid()
-            gg = gg.tanh()
-            cl = gf * cmt + gi * gg
-            hl = go * cl.tanh()
-            outs.append(hl)
-        layer_in = torch.stack(outs)
-        h = torch.cat([h[:l], hl.unsqueeze(0), h[l + 1:]])
-        c = torch.cat([c[:l], cl.unsqueeze(0), c[l + 1:]])
-    return layer_in, (h, c)
 
 
 @pytest.mark.parametrize("L,H,use_done", [(1, 32, True), (2, 519, True),
