@@ -8,6 +8,7 @@ and defaults match the reference exactly (unroll 80, batch 8, RMSProp
 """
 
 import argparse
+import os
 
 
 def add_common_flags(parser: argparse.ArgumentParser):
@@ -27,7 +28,20 @@ def add_common_flags(parser: argparse.ArgumentParser):
     parser.add_argument("--unroll_length", default=80, type=int, metavar="T",
                         help="Unroll length (time dimension).")
     parser.add_argument("--disable_cuda", action="store_true", help="Disable CUDA.")
+    parser.add_argument("--resnet_any_geometry", action="store_true",
+                        help="Run the deep ResNet on the run-time-geometry "
+                             "MFMA conv kernels at frame sizes other than "
+                             "84x84 (up to 256x256), in the learner and the "
+                             "C++ runner; same as TBAMD_RESNET_ANY=1.")
     return parser
+
+
+def apply_resnet_any_geometry(flags):
+    """--resnet_any_geometry -> TBAMD_RESNET_ANY=1, which the model reads at
+    every forward and the C++ runner at construction; call before either
+    exists. Without the flag the environment is left as it is."""
+    if getattr(flags, "resnet_any_geometry", False):
+        os.environ["TBAMD_RESNET_ANY"] = "1"
 
 
 def add_loss_flags(parser: argparse.ArgumentParser):

@@ -7,6 +7,9 @@ with ReLU / max-pool / residual adds on bf16 channels_last ATen ops. The
 first conv (CI = observation channels, e.g. 4) stays on ATen — its K-runs
 are narrower than an MFMA A-fragment. Features are flattened in logical
 NCHW order in both paths so checkpoints transfer between CPU and GPU.
+With TBAMD_RESNET_ANY=1 (--resnet_any_geometry) every other frame size up
+to 256x256 takes the same path on the run-time-geometry kernels
+(conv_any_kernel / wgrad_any_kernel); unset, those frames stay on ATen.
 
 Three feature sections with channel widths [16, 32, 32]; each section is a
 3x3 s1 p1 conv, a 3x3 s2 p1 max-pool, and two residual blocks of
@@ -80,7 +83,9 @@ class ResNet(nn.Module):
         self.baseline = nn.Linear(core_size, 1)
 
     def _features_mfma(self, x):
-        """84x84 trunk on the MFMA conv kernels, bf16 channels_last."""
+        """Trunk on the MFMA conv kernels, bf16 channels_last: the template
+        kernels at the 84x84 geometries, the run-time-geometry ones at any
+        other (H, W)."""
         from torchbeast_amd.ops import functional as tbf
 
         cl = torch.channels_last
@@ -102,12 +107,36 @@ class ResNet(nn.Module):
         x = res_block(s3.res1, res_block(s3.res0, x))
         return x.float()
 
+    @staticmethod
+    def _any_geometry_supported(h, w):
+        """Every conv of the three sections, forward and backward, at an
+        (h, w) frame: each max-pool takes a size to (size + 1) // 2."""
+        from torchbeast_amd.ops import functional as tbf
+
+        convs = [(8, h, w, 16)]
+        ci = 16
+        for co in (16, 32, 32):
+            if co != ci:  # the section's feature conv and its dgrad
+                convs += [(ci, h, w, co), (co, h, w, ci)]
+            elif ci == 32:
+                convs.append((ci, h, w, co))
+            h, w = (h + 1) // 2, (w + 1) // 2
+            convs.append((co, h, w, co))  # the residual convs
+            ci = co
+        return all(tbf.resnet_conv_any_supported(*c) for c in convs)
+
     def _features(self, x):
-        if (x.is_cuda and x.shape[2:] == (84, 84) and x.shape[1] <= 8
+        if (x.is_cuda and x.shape[1] <= 8
                 and os.environ.get("TBAMD_RESNET") != "aten"):
             from torchbeast_amd.ops import functional as tbf
 
-            if tbf.resnet_conv3x3_supported(16, 42, 16):
+            if x.shape[2:] == (84, 84):
+                if tbf.resnet_conv3x3_supported(16, 42, 16):
+                    return self._features_mfma(x)
+            elif (os.environ.get("TBAMD_RESNET_ANY") == "1"
+                    and self._any_geometry_supported(*x.shape[2:])):
+                # Opt-in: any other frame size on the run-time-geometry
+                # MFMA kernels instead of fp32 library convs.
                 return self._features_mfma(x)
         return self.feat_extract(x)
 

@@ -297,6 +297,7 @@ def learn(
 
 
 def train(flags):  # noqa: C901
+    tbflags.apply_resnet_any_geometry(flags)
     if flags.xpid is None:
         flags.xpid = time.strftime("torchbeast-%Y%m%d-%H%M%S")
     plogger = file_writer.FileWriter(

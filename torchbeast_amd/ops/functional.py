@@ -489,10 +489,18 @@ class _ResNetConv3x3(torch.autograd.Function):
         ci, hw, co = x.shape[1], x.shape[2], weight.shape[0]
         ext = _ext_for(x, "resnet_conv")
         wp = _pack_resnet_weight(weight)
-        out = ext.resnet_conv(x, wp, bias.detach().float().contiguous(),
-                              ci, hw, co, True)
+        # The six template geometries keep their kernels; every other
+        # (H, W) runs the run-time-geometry ones.
+        fixed = _resnet_fixed_geometry(ext, ci, hw, x.shape[3], co)
+        if fixed:
+            out = ext.resnet_conv(x, wp, bias.detach().float().contiguous(),
+                                  ci, hw, co, True)
+        else:
+            out = ext.resnet_conv_any(
+                x, wp, bias.detach().float().contiguous(), True)
         ctx.save_for_backward(x, weight)
         ctx.geom = (ci, hw, co)
+        ctx.fixed = fixed
         # NHWC-dense result presented as logical NCHW (channels_last view).
         return out.permute(0, 3, 1, 2)
 
@@ -504,9 +512,14 @@ class _ResNetConv3x3(torch.autograd.Function):
         dyn = (dy.to(torch.bfloat16)
                .contiguous(memory_format=torch.channels_last))
         wr = _pack_resnet_weight(weight, rotate=True)
-        dx = ext.resnet_conv(dyn, wr, dyn.new_empty(0).float(),
-                             co, hw, ci, False).permute(0, 3, 1, 2)
-        dwp, db = ext.resnet_conv_wgrad(x, dyn, ci, hw, co)
+        if ctx.fixed:
+            dx = ext.resnet_conv(dyn, wr, dyn.new_empty(0).float(),
+                                 co, hw, ci, False)
+            dwp, db = ext.resnet_conv_wgrad(x, dyn, ci, hw, co)
+        else:
+            dx = ext.resnet_conv_any(dyn, wr, dyn.new_empty(0).float(), False)
+            dwp, db = ext.resnet_conv_any_wgrad(x, dyn)
+        dx = dx.permute(0, 3, 1, 2)
         # [ky][co][kx*ci+c] (K-cols padded to 16) -> [co][ci][kh][kw].
         dw = (dwp[:, :, :3 * ci].view(3, co, 3, ci)
               .permute(1, 3, 0, 2).contiguous())
@@ -533,11 +546,18 @@ class _ResNetFirstConv(torch.autograd.Function):
             [weight.detach(),
              weight.new_zeros(co, 8 - ci, *weight.shape[2:])], dim=1)
         ext = _ext_for(x8, "resnet_conv")
-        out = ext.resnet_conv(x8, _pack_resnet_weight(w8),
-                              bias.detach().float().contiguous(),
-                              8, x8.shape[2], co, True)
+        fixed = _resnet_fixed_geometry(ext, 8, x8.shape[2], x8.shape[3], co)
+        if fixed:
+            out = ext.resnet_conv(x8, _pack_resnet_weight(w8),
+                                  bias.detach().float().contiguous(),
+                                  8, x8.shape[2], co, True)
+        else:
+            out = ext.resnet_conv_any(x8, _pack_resnet_weight(w8),
+                                      bias.detach().float().contiguous(),
+                                      True)
         ctx.save_for_backward(x8)
         ctx.ci = ci
+        ctx.fixed = fixed
         return out.permute(0, 3, 1, 2)
 
     @staticmethod
@@ -547,14 +567,17 @@ class _ResNetFirstConv(torch.autograd.Function):
         dyn = (dy.to(torch.bfloat16)
                .contiguous(memory_format=torch.channels_last))
         co = dyn.shape[1]
-        dwp, db = ext.resnet_conv_wgrad(x8, dyn, 8, x8.shape[2], co)
+        if ctx.fixed:
+            dwp, db = ext.resnet_conv_wgrad(x8, dyn, 8, x8.shape[2], co)
+        else:
+            dwp, db = ext.resnet_conv_any_wgrad(x8, dyn)
         dw = (dwp[:, :, :24].view(3, co, 3, 8).permute(1, 3, 0, 2)
               [:, :ctx.ci].contiguous())
         return None, dw, db
 
 
 def resnet_first_conv(conv, x):
-    """x: fp32 [N, C<=8, 84, 84] frames (no grad); returns bf16
+    """x: fp32 [N, C<=8, H, W] frames (no grad); returns bf16
     channels_last conv output."""
     n, c = x.shape[0], x.shape[1]
     x8 = torch.empty((n, 8, *x.shape[2:]), dtype=torch.bfloat16,
@@ -562,6 +585,21 @@ def resnet_first_conv(conv, x):
     x8.zero_()
     x8[:, :c] = x
     return _ResNetFirstConv.apply(x8, conv.weight, conv.bias)
+
+
+def _resnet_fixed_geometry(ext, ci, h, w, co):
+    """True for the square geometries the template kernels are built for."""
+    return h == w and bool(ext.resnet_conv_supported(ci, h, co))
+
+
+def resnet_conv_any_supported(ci, h, w, co):
+    """Can the run-time-geometry kernels run this 3x3 s1 p1 conv?"""
+    try:
+        import torchbeast_amd.ops as _ops
+        ext = _ops.require_ext()
+    except Exception:  # noqa: BLE001
+        return False
+    return bool(ext.resnet_conv_any_supported(ci, h, w, co))
 
 
 def resnet_conv3x3_supported(ci, hw, co):

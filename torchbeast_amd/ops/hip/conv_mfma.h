@@ -55,4 +55,15 @@ std::vector<torch::Tensor> resnet_conv_wgrad(torch::Tensor x,
                                              torch::Tensor dy, int64_t ci,
                                              int64_t hw, int64_t co);
 
+// The same conv with H and W taken at run time (1..256 each, planned by
+// conv_any_plan.h), geometry read from the tensors. x: bf16 channels_last
+// [N,CI,H,W]; w, bias as for resnet_conv. Returns bf16 NHWC [N,H,W,CO].
+// Operands are validated on the host before any launch.
+torch::Tensor resnet_conv_any(torch::Tensor x, torch::Tensor w,
+                              torch::Tensor bias, bool fwd);
+bool resnet_conv_any_supported(int64_t ci, int64_t h, int64_t w, int64_t co);
+// x, dy: bf16 channels_last [N,CI,H,W], [N,CO,H,W].
+std::vector<torch::Tensor> resnet_conv_any_wgrad(torch::Tensor x,
+                                                 torch::Tensor dy);
+
 }  // namespace tbamd

@@ -40,6 +40,7 @@
 
 #include <vector>
 
+#include "conv_any_plan.h"
 #include "conv_mfma.h"
 
 namespace tbamd {
@@ -1076,6 +1077,407 @@ std::vector<torch::Tensor> resnet_conv_wgrad(torch::Tensor x,
     return run_wgrad<32, 11, 11, 3, 3, 1, 32, 11, 11, 1024, false, 1>(x, dy);
   }
   TORCH_CHECK(false, "resnet_conv_wgrad: unsupported geometry");
+}
+
+// ---------------------------------------------------------------------------
+// The same 3x3 s1 p1 conv with H and W taken at run time (any 1..256), so
+// the deep net runs on MFMA kernels at every frame size. CI, CO, the mode
+// and the per-wave accumulator capacity stay template parameters; the band
+// height, LDS size and wgrad chunking come from conv_any_plan.h. Design as
+// conv_nhwc_kernel / wgrad_kernel above: padded band tile staged once in
+// swizzled LDS, barrier-free K-loop, weight fragments from global memory,
+// fp32 accumulation, tails handled by masking.
+// ---------------------------------------------------------------------------
+
+namespace {
+
+struct ConvAnyArgs {
+  int H, W, R, N;
+  uint32_t magic_w, magic_cpr;
+};
+
+template <int CI, int CO, int MODE, int CAP>
+__global__ __launch_bounds__(kThreads) void conv_any_kernel(
+    const __bf16* __restrict__ in,   // [N, H, W, CI]
+    const __bf16* __restrict__ Wt,   // [CO, KP] (ky,kx,c)-major, zero-padded
+    const float* __restrict__ bias,  // [CO] (MODE 5)
+    __bf16* __restrict__ out,        // [N, H, W, CO]
+    ConvAnyArgs g) {
+  constexpr int KWC = 3 * CI;
+  constexpr int K = 9 * CI;
+  constexpr int KP = ((K + 31) / 32) * 32;
+  constexpr int NF = CO / 16;
+  constexpr bool kKyUniform = (KWC % 32) == 0;
+  static_assert(CI % 8 == 0, "staging chunks must lie within one x");
+  static_assert(MODE == 3 || MODE == 5, "5: fwd + bias, 3: plain dgrad");
+
+  extern __shared__ char smem[];  // (R + 2) * ROWE bf16, swizzled
+
+  const int H = g.H, W = g.W, R = g.R;
+  const int ROWE = (W + 2) * CI;  // elements per staged row
+  const int cpr = ROWE / 8;       // 16 B chunks per staged row
+  const int64_t s = blockIdx.x;
+  const int oy0 = blockIdx.y * R;
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6;
+  const int lane = tid & 63;
+  const int ln = lane & 15;
+  const int lg = lane >> 4;
+
+  // ---- stage rows oy0-1 .. oy0+R of the zero-padded input ----
+  {
+    const int nchunk = (R + 2) * cpr;
+    const __bf16* base = in + s * H * W * CI;
+    for (int idx = tid; idx < nchunk; idx += kThreads) {
+      const int row = __umulhi((uint32_t)idx, g.magic_cpr);
+      const int xo = (idx - row * cpr) * 8;
+      const int ry = oy0 + row - 1, rx = xo / CI - 1, c = xo % CI;
+      bf16x8 v = {};
+      if (ry >= 0 && ry < H && rx >= 0 && rx < W) {
+        v = *reinterpret_cast<const bf16x8*>(
+            &base[((int64_t)ry * W + rx) * CI + c]);
+      }
+      lds_write8_swz(smem, idx * 8, v);
+    }
+  }
+  __syncthreads();
+
+  const int m_blk = R * W;
+  const int mf = (m_blk + 15) >> 4;
+  const int mvalid = min(R, H - oy0) * W;
+
+  int aoff[CAP];
+  int nmf = 0;
+#pragma unroll
+  for (int i = 0; i < CAP; ++i) {
+    const int f = wave + i * kWaves;
+    if (f < mf) ++nmf;
+    const int m = min(f * 16 + ln, m_blk - 1);
+    const int oy = (int)(((uint32_t)m * g.magic_w) >> 20);  // m / W
+    // oy * ROWE + ox * CI with ox = m - oy * W.
+    aoff[i] = (m + 2 * oy) * CI;
+  }
+
+  f32x4 acc[CAP][NF];
+#pragma unroll
+  for (int f = 0; f < CAP; ++f)
+#pragma unroll
+    for (int j = 0; j < NF; ++j) acc[f][j] = {0.f, 0.f, 0.f, 0.f};
+
+#pragma unroll
+  for (int ks = 0; ks < KP / 32; ++ks) {
+    const int k0 = ks * 32;
+    bf16x8 bfr[NF];
+#pragma unroll
+    for (int j = 0; j < NF; ++j) {
+      bfr[j] = *reinterpret_cast<const bf16x8*>(
+          &Wt[(j * 16 + ln) * KP + k0 + 8 * lg]);
+    }
+    int rowoff;
+    if (kKyUniform) {
+      rowoff = (k0 / KWC) * ROWE + k0 % KWC + 8 * lg;
+    } else {
+      // Per-lane-group ky; K-pad lanes read LDS offset 0 (finite) and the
+      // zero-padded weight columns annihilate the products.
+      const int k = k0 + 8 * lg;
+      rowoff = (KP == K || k < K) ? (k / KWC) * ROWE + k % KWC : 0;
+    }
+#pragma unroll
+    for (int f = 0; f < CAP; ++f) {
+      if (f >= nmf) break;
+      const bf16x8 a = lds_read8_swz(smem, aoff[f] + rowoff);
+#pragma unroll
+      for (int j = 0; j < NF; ++j) {
+        acc[f][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bfr[j],
+                                                            acc[f][j], 0, 0, 0);
+      }
+    }
+  }
+
+  // ---- epilogue: the band's outputs are contiguous in m ----
+  __bf16* obase = out + (s * H + oy0) * W * CO;
+#pragma unroll
+  for (int f = 0; f < CAP; ++f) {
+    if (f >= nmf) break;
+#pragma unroll
+    for (int j = 0; j < NF; ++j) {
+      const int cch = j * 16 + ln;
+      const float b = MODE == 5 ? bias[cch] : 0.f;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int m = (wave + f * kWaves) * 16 + lg * 4 + r;
+        if (m < mvalid) obase[(int64_t)m * CO + cch] = (__bf16)(acc[f][j][r] + b);
+      }
+    }
+  }
+}
+
+struct WgradAnyArgs {
+  int H, W, MC;
+  uint32_t M;  // N * H * W < 2^31
+  uint32_t magic_hw, magic_w;
+};
+
+__device__ __forceinline__ uint32_t div_magic(uint32_t m, uint32_t d,
+                                              uint32_t magic) {
+  uint32_t q = __umulhi(m, magic);  // short by at most one (conv_any_plan.h)
+  if (m - q * d >= d) ++q;
+  return q;
+}
+
+// grid = (chunks, 3 ky slices); partial layout as wgrad_kernel.
+template <int CI, int CO>
+__global__ __launch_bounds__(kThreads) void wgrad_any_kernel(
+    const __bf16* __restrict__ xb,    // [N, H, W, CI]
+    const __bf16* __restrict__ dy,    // [N, H, W, CO]
+    float* __restrict__ partials,     // [nchunks, 3, CO, KWCP]
+    float* __restrict__ db_partials,  // [nchunks, CO]
+    WgradAnyArgs g) {
+  constexpr int KWC = 3 * CI;
+  constexpr int KWCP = ((KWC + 15) / 16) * 16;
+  constexpr int MPAD = 64;
+  constexpr int MSTEP = 64;
+  constexpr int OF = (CO / 16) * (KWCP / 16);
+  constexpr int PER_WAVE = (OF + kWaves - 1) / kWaves;
+  static_assert(CI % 8 == 0, "staging chunks must lie within one kx");
+
+  __shared__ char sDYT[CO * MPAD * 2];
+  __shared__ char sXT[KWCP * MPAD * 2];
+  auto stage = [](char* buf, int row, int col, __bf16 v) {
+    *reinterpret_cast<__bf16*>(buf + swz((row * MPAD + col) * 2)) = v;
+  };
+
+  const int H = g.H, W = g.W;
+  const uint32_t HW = (uint32_t)(H * W);
+  const uint32_t chunk = blockIdx.x;
+  const int ky = blockIdx.y;
+  const uint32_t M = g.M;
+  const uint32_t m0 = chunk * (uint32_t)g.MC;
+  const uint32_t mend = min(m0 + (uint32_t)g.MC, M);
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6;
+  const int lane = tid & 63;
+  const int ln = lane & 15;
+  const int lg = lane >> 4;
+
+  f32x4 acc[PER_WAVE];
+#pragma unroll
+  for (int i = 0; i < PER_WAVE; ++i) acc[i] = {0.f, 0.f, 0.f, 0.f};
+  float db = 0.f;
+  // Zero the K-column pad rows once (staging never writes them).
+  for (int i = tid; i < (KWCP - KWC) * MPAD; i += kThreads) {
+    stage(sXT, KWC + i / MPAD, i % MPAD, (__bf16)0.f);
+  }
+  if (KWCP != KWC) __syncthreads();
+
+  for (uint32_t ms = m0; ms < mend; ms += MSTEP) {
+    // ---- transpose-stage dY[ms..ms+MSTEP) ----
+    for (int idx = tid; idx < MSTEP * (CO / 8); idx += kThreads) {
+      const int mm = idx / (CO / 8);
+      const int ch = (idx % (CO / 8)) * 8;
+      bf16x8 v = {};
+      if (ms + mm < mend) {
+        v = *reinterpret_cast<const bf16x8*>(&dy[(int64_t)(ms + mm) * CO + ch]);
+      }
+#pragma unroll
+      for (int i = 0; i < 8; ++i) stage(sDYT, ch + i, mm, v[i]);
+    }
+    // ---- transpose-stage the X spans of this ky: a chunk of 8 channels
+    // lies within one kx, so the border guard is per chunk ----
+    for (int idx = tid; idx < MSTEP * (KWC / 8); idx += kThreads) {
+      const int mm = idx / (KWC / 8);
+      const int ch = (idx % (KWC / 8)) * 8;
+      const uint32_t m = ms + mm;
+      bf16x8 v = {};
+      if (m < mend) {
+        const uint32_t s = div_magic(m, HW, g.magic_hw);
+        const uint32_t rm = m - s * HW;
+        const int oy = (int)div_magic(rm, (uint32_t)W, g.magic_w);
+        const int ox = (int)rm - oy * W;
+        const int iy = oy + ky - 1;
+        const int ix = ox + ch / CI - 1;
+        if (iy >= 0 && iy < H && ix >= 0 && ix < W) {
+          v = *reinterpret_cast<const bf16x8*>(
+              &xb[(((int64_t)s * H + iy) * W + ix) * CI + ch % CI]);
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < 8; ++i) stage(sXT, ch + i, mm, v[i]);
+    }
+    __syncthreads();
+
+#pragma unroll
+    for (int i = 0; i < PER_WAVE; ++i) {
+      const int of = wave * PER_WAVE + i;
+      if (of >= OF) break;
+      const int ni = of / (KWCP / 16);
+      const int ki = of % (KWCP / 16);
+#pragma unroll
+      for (int half = 0; half < MSTEP / 32; ++half) {
+        const bf16x8 a = lds_read8_swz(
+            sDYT, (ni * 16 + ln) * MPAD + half * 32 + 8 * lg);
+        const bf16x8 b = lds_read8_swz(
+            sXT, (ki * 16 + ln) * MPAD + half * 32 + 8 * lg);
+        acc[i] =
+            __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc[i], 0, 0, 0);
+      }
+    }
+    // db: wave 0 of the ky == 0 blocks, one lane per output channel.
+    if (ky == 0 && wave == 0 && lane < CO) {
+#pragma unroll
+      for (int ch = 0; ch < MSTEP / 8; ++ch) {
+        const bf16x8 v = lds_read8_swz(sDYT, lane * MPAD + ch * 8);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) db += (float)v[i];
+      }
+    }
+    __syncthreads();
+  }
+
+  float* pbase = partials + ((int64_t)chunk * 3 + ky) * CO * KWCP;
+#pragma unroll
+  for (int i = 0; i < PER_WAVE; ++i) {
+    const int of = wave * PER_WAVE + i;
+    if (of >= OF) break;
+    const int ni = of / (KWCP / 16);
+    const int ki = of % (KWCP / 16);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      pbase[(ni * 16 + lg * 4 + r) * KWCP + ki * 16 + ln] = acc[i][r];
+    }
+  }
+  if (ky == 0 && wave == 0 && lane < CO) {
+    db_partials[(int64_t)chunk * CO + lane] = db;
+  }
+}
+
+template <int CI, int CO, int MODE, int CAP>
+void launch_conv_any(const torch::Tensor& x, const torch::Tensor& w,
+                     const float* bias_p, torch::Tensor& out,
+                     const ConvAnyPlan& p, const ConvAnyArgs& a) {
+  hipLaunchKernelGGL((conv_any_kernel<CI, CO, MODE, CAP>),
+                     dim3((uint32_t)a.N, (uint32_t)p.bands), dim3(kThreads),
+                     (size_t)p.lds_bytes, at::cuda::getCurrentCUDAStream(),
+                     reinterpret_cast<const __bf16*>(x.data_ptr()),
+                     reinterpret_cast<const __bf16*>(w.data_ptr()), bias_p,
+                     reinterpret_cast<__bf16*>(out.data_ptr()), a);
+}
+
+template <int CI, int CO>
+void dispatch_conv_any(const torch::Tensor& x, const torch::Tensor& w,
+                       const float* bias_p, torch::Tensor& out,
+                       const ConvAnyPlan& p, const ConvAnyArgs& a, bool fwd) {
+  if (fwd) {
+    if (p.cap == 2) launch_conv_any<CI, CO, 5, 2>(x, w, bias_p, out, p, a);
+    else launch_conv_any<CI, CO, 5, kConvAnyMaxCap>(x, w, bias_p, out, p, a);
+  } else {
+    if (p.cap == 2) launch_conv_any<CI, CO, 3, 2>(x, w, bias_p, out, p, a);
+    else launch_conv_any<CI, CO, 3, kConvAnyMaxCap>(x, w, bias_p, out, p, a);
+  }
+}
+
+template <int CI, int CO>
+std::vector<torch::Tensor> run_wgrad_any(const torch::Tensor& x,
+                                         const torch::Tensor& dy,
+                                         const ConvAnyPlan& p,
+                                         const WgradAnyArgs& a) {
+  constexpr int KWCP = ((3 * CI + 15) / 16) * 16;
+  auto fopt = dy.options().dtype(torch::kFloat32);
+  auto partials = torch::empty({p.nchunks, 3, CO, KWCP}, fopt);
+  auto db_partials = torch::empty({p.nchunks, CO}, fopt);
+  auto dW = torch::empty({3, CO, KWCP}, fopt);
+  auto db = torch::empty({CO}, fopt);
+  auto stream = at::cuda::getCurrentCUDAStream();
+  hipLaunchKernelGGL((wgrad_any_kernel<CI, CO>),
+                     dim3((uint32_t)p.nchunks, 3), dim3(kThreads), 0, stream,
+                     reinterpret_cast<const __bf16*>(x.data_ptr()),
+                     reinterpret_cast<const __bf16*>(dy.data_ptr()),
+                     partials.data_ptr<float>(),
+                     db_partials.data_ptr<float>(), a);
+  const int64_t stride = (int64_t)3 * CO * KWCP;
+  hipLaunchKernelGGL(reduce_partials_kernel,
+                     dim3((int)std::min<int64_t>((stride + 255) / 256, 1024)),
+                     dim3(256), 0, stream, partials.data_ptr<float>(),
+                     dW.data_ptr<float>(), (int)p.nchunks, stride);
+  hipLaunchKernelGGL(reduce_partials_kernel, dim3(1), dim3(256), 0, stream,
+                     db_partials.data_ptr<float>(), db.data_ptr<float>(),
+                     (int)p.nchunks, CO);
+  return {dW, db};
+}
+
+void check_any_operand(const torch::Tensor& t, const char* what) {
+  TORCH_CHECK(t.is_cuda(), what, ": GPU tensor required");
+  TORCH_CHECK(t.scalar_type() == torch::kBFloat16, what, ": bf16 required");
+  TORCH_CHECK(t.dim() == 4 && t.is_contiguous(at::MemoryFormat::ChannelsLast),
+              what, ": channels_last [N, C, H, W] required");
+}
+
+}  // namespace
+
+bool resnet_conv_any_supported(int64_t ci, int64_t h, int64_t w, int64_t co) {
+  return conv_any_plan(ci, h, w, co, 1).ok;
+}
+
+// x: bf16 channels_last [N, CI, H, W]; w: bf16 [CO, ceil32(9*CI)] packed as
+// for resnet_conv; bias fp32 [CO] for fwd, empty for dgrad (pre-rotated w).
+// Returns bf16 NHWC [N, H, W, CO].
+torch::Tensor resnet_conv_any(torch::Tensor x, torch::Tensor w,
+                              torch::Tensor bias, bool fwd) {
+  check_any_operand(x, "resnet_conv_any x");
+  TORCH_CHECK(w.is_cuda() && w.scalar_type() == torch::kBFloat16 &&
+                  w.dim() == 2 && w.is_contiguous(),
+              "resnet_conv_any w: contiguous bf16 [CO, K] GPU tensor required");
+  const int64_t N = x.size(0), ci = x.size(1), H = x.size(2), Wd = x.size(3);
+  const int64_t co = w.size(0);
+  TORCH_CHECK(w.size(1) == (9 * ci + 31) / 32 * 32,
+              "resnet_conv_any: w has K = ", w.size(1), ", want ceil32(9 * ",
+              ci, ")");
+  TORCH_CHECK(fwd == (bias.numel() > 0), "fwd needs bias, dgrad must not");
+  if (fwd) {
+    TORCH_CHECK(bias.is_cuda() && bias.scalar_type() == torch::kFloat32 &&
+                    bias.is_contiguous() && bias.numel() == co,
+                "resnet_conv_any bias: contiguous fp32 [CO] GPU tensor");
+  }
+  TORCH_CHECK(conv_any_channels_ok(ci, co) && H >= 1 && Wd >= 1 &&
+                  H <= kConvAnyMaxDim && Wd <= kConvAnyMaxDim,
+              "resnet_conv_any: unsupported geometry ci=", ci, " h=", H,
+              " w=", Wd, " co=", co);
+  auto out = torch::empty({N, H, Wd, co}, w.options());
+  if (N == 0) return out;
+  const ConvAnyPlan p = conv_any_plan(ci, H, Wd, co, N);
+  TORCH_CHECK(p.ok, "resnet_conv_any: batch of ", N, " too large");
+  const ConvAnyArgs a{(int)H, (int)Wd, p.rows, (int)N, p.magic_w, p.magic_cpr};
+  const float* bias_p = fwd ? bias.data_ptr<float>() : nullptr;
+  if (ci == 8) dispatch_conv_any<8, 16>(x, w, bias_p, out, p, a, fwd);
+  else if (ci == 16 && co == 16)
+    dispatch_conv_any<16, 16>(x, w, bias_p, out, p, a, fwd);
+  else if (ci == 16) dispatch_conv_any<16, 32>(x, w, bias_p, out, p, a, fwd);
+  else if (co == 16) dispatch_conv_any<32, 16>(x, w, bias_p, out, p, a, fwd);
+  else dispatch_conv_any<32, 32>(x, w, bias_p, out, p, a, fwd);
+  return out;
+}
+
+// {dW [3, CO, KWCP] fp32, db [CO] fp32} in resnet_conv_wgrad's layout.
+std::vector<torch::Tensor> resnet_conv_any_wgrad(torch::Tensor x,
+                                                 torch::Tensor dy) {
+  check_any_operand(x, "resnet_conv_any_wgrad x");
+  check_any_operand(dy, "resnet_conv_any_wgrad dy");
+  const int64_t N = x.size(0), ci = x.size(1), H = x.size(2), Wd = x.size(3);
+  const int64_t co = dy.size(1);
+  TORCH_CHECK(dy.size(0) == N && dy.size(2) == H && dy.size(3) == Wd,
+              "resnet_conv_any_wgrad: x ", x.sizes(), " and dy ", dy.sizes(),
+              " disagree");
+  TORCH_CHECK(N >= 1, "resnet_conv_any_wgrad: empty batch");
+  const ConvAnyPlan p = conv_any_plan(ci, H, Wd, co, N);
+  TORCH_CHECK(p.ok, "resnet_conv_any_wgrad: unsupported geometry ci=", ci,
+              " h=", H, " w=", Wd, " co=", co, " n=", N);
+  const WgradAnyArgs a{(int)H, (int)Wd, p.mc, (uint32_t)(N * H * Wd),
+                       p.magic_hw, p.magic_w32};
+  if (ci == 8) return run_wgrad_any<8, 16>(x, dy, p, a);
+  if (ci == 16 && co == 16) return run_wgrad_any<16, 16>(x, dy, p, a);
+  if (ci == 16) return run_wgrad_any<16, 32>(x, dy, p, a);
+  if (co == 16) return run_wgrad_any<32, 16>(x, dy, p, a);
+  return run_wgrad_any<32, 32>(x, dy, p, a);
 }
 
 }  // namespace tbamd

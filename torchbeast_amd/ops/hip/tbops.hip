@@ -784,6 +784,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("resnet_conv", &tbamd::resnet_conv);
   m.def("resnet_conv_supported", &tbamd::resnet_conv_supported);
   m.def("resnet_conv_wgrad", &tbamd::resnet_conv_wgrad);
+  m.def("resnet_conv_any", &tbamd::resnet_conv_any);
+  m.def("resnet_conv_any_supported", &tbamd::resnet_conv_any_supported);
+  m.def("resnet_conv_any_wgrad", &tbamd::resnet_conv_any_wgrad);
   m.def("barrier_probe", &tbamd::barrier_probe);
   m.def("launch_probe", &tbamd::launch_probe);
   m.def("mfma_gemm", &tbamd::mfma_gemm);

@@ -392,6 +392,7 @@ def learn(
 
 
 def train(flags):  # noqa: C901
+    tbflags.apply_resnet_any_geometry(flags)
     rank, world_size, local_rank = tbddp.maybe_init_distributed()
     is_leader = rank == 0
     torch.manual_seed(4242 + rank * 977)

@@ -73,7 +73,8 @@ class InferenceRunner {
     TORCH_CHECK(weights_[0].is_cuda(), "runner weights must be on the GPU");
     device_ = weights_[0].device();
     // Deep 84x84 trunk serves on the hand-written MFMA 3x3 kernels
-    // (conv_mfma.hip resnet_conv); MIOpen only for other geometries.
+    // (conv_mfma.hip resnet_conv); MIOpen for other geometries, unless
+    // TBAMD_RESNET_ANY=1 puts those on resnet_conv_any (see trunk()).
     deep_mfma_ = deep_ && !aten_only_ && weights_[0].size(0) == 16 &&
                  weights_[0].size(1) <= 8 && weights_[0].size(2) == 3 &&
                  tbamd::resnet_conv_supported(16, 42, 16);
@@ -561,7 +562,11 @@ class InferenceRunner {
   torch::Tensor trunk(const ServeInputs& in, at::cuda::CUDAStream& stream) {
     const int64_t bp = in.bp, C = in.C, H = in.H, W = in.W;
     torch::Tensor x;
-    if (deep_ && deep_mfma_ && H == 84 && W == 84 && C <= 8) {
+    if (deep_ && deep_mfma_ && C <= 8 &&
+        ((H == 84 && W == 84) || (resnet_any_ && deep_any_supported(H, W)))) {
+      // 84x84 on the template kernels; with TBAMD_RESNET_ANY=1 every other
+      // supported frame size on the run-time-geometry ones. No MIOpen runs
+      // on either, so neither needs the first-serve lock.
       x = trunk_deep_mfma(in, packed_weights(stream));
     } else if (deep_) {
       x = in.frames.to(torch::kFloat32).mul_(1.0f / 255.0f);
@@ -611,9 +616,23 @@ class InferenceRunner {
   }
 
   // bf16 channels_last ResNet trunk, every conv on the MFMA template.
+  // Every forward conv of the three sections at an (H, W) frame.
+  static bool deep_any_supported(int64_t h, int64_t w) {
+    const int64_t widths[3] = {16, 32, 32};
+    int64_t ci = 8;
+    for (int sec = 0; sec < 3; ++sec) {
+      if (!tbamd::resnet_conv_any_supported(ci, h, w, widths[sec])) return false;
+      h = (h + 1) / 2;
+      w = (w + 1) / 2;
+      ci = widths[sec];
+      if (!tbamd::resnet_conv_any_supported(ci, h, w, ci)) return false;
+    }
+    return true;
+  }
+
   torch::Tensor trunk_deep_mfma(const ServeInputs& in,
                                 const std::vector<torch::Tensor>& wp) {
-    auto x8 = torch::empty({in.bp, 8, 84, 84},
+    auto x8 = torch::empty({in.bp, 8, in.H, in.W},
                            torch::TensorOptions().device(device_).dtype(
                                torch::kBFloat16),
                            torch::MemoryFormat::ChannelsLast);
@@ -621,24 +640,32 @@ class InferenceRunner {
     x8.narrow(1, 0, in.C).copy_(in.frames, /*non_blocking=*/true);
     x8.mul_(1.0f / 255.0f);
     size_t wi = 0, pi = 0;
-    auto conv = [&](torch::Tensor t, int64_t ci, int64_t hw, int64_t co) {
-      auto o = tbamd::resnet_conv(t, wp[pi], weights_[wi + 1], ci, hw, co,
-                                  /*fwd=*/true);
+    // The template geometries keep their kernels; any other (h, w) runs
+    // the run-time-geometry ones (trunk() has checked they are supported).
+    auto conv = [&](torch::Tensor t, int64_t ci, int64_t h, int64_t w,
+                    int64_t co) {
+      auto o = (h == w && tbamd::resnet_conv_supported(ci, h, co))
+                   ? tbamd::resnet_conv(t, wp[pi], weights_[wi + 1], ci, h, co,
+                                        /*fwd=*/true)
+                   : tbamd::resnet_conv_any(
+                         t.contiguous(torch::MemoryFormat::ChannelsLast),
+                         wp[pi], weights_[wi + 1], /*fwd=*/true);
       ++pi;
       wi += 2;
       return o.permute({0, 3, 1, 2});
     };
     const int64_t widths[3] = {16, 32, 32};
-    int64_t hw = 84, ci = 8;
+    int64_t h = in.H, w = in.W, ci = 8;
     torch::Tensor t = x8;
     for (int sec = 0; sec < 3; ++sec) {
-      t = conv(t, ci, hw, widths[sec]);
+      t = conv(t, ci, h, w, widths[sec]);
       t = at::max_pool2d(t, 3, 2, 1);
-      hw = (hw + 1) / 2;
+      h = (h + 1) / 2;
+      w = (w + 1) / 2;
       ci = widths[sec];
       for (int res = 0; res < 2; ++res) {
-        torch::Tensor y = conv(at::relu(t), ci, hw, ci);
-        y = conv(at::relu(y), ci, hw, ci);
+        torch::Tensor y = conv(at::relu(t), ci, h, w, ci);
+        y = conv(at::relu(y), ci, h, w, ci);
         t = t + y;
       }
     }
@@ -959,6 +986,11 @@ class InferenceRunner {
   // Benchmarking: serve everything through library ops (the strategy
   // comparison in scripts/inference_speed_profiling.py).
   const bool aten_only_ = std::getenv("TBAMD_RUNNER_ATEN") != nullptr;
+  // TBAMD_RESNET_ANY=1: deep frames other than 84x84 on the MFMA kernels.
+  const bool resnet_any_ = [] {
+    const char* v = std::getenv("TBAMD_RESNET_ANY");
+    return v != nullptr && v[0] == '1' && v[1] == '\0';
+  }();
   const bool serve_timing_ = std::getenv("TBAMD_SERVE_TIMINGS") != nullptr;
   const bool trace_ = std::getenv("TBAMD_SERVE_TRACE") != nullptr;
   // TBAMD_ACTOR_FASTPATH=0: tensor serve code only (A/B against rows).
@@ -984,7 +1016,8 @@ class InferenceRunner {
   const int64_t num_lstm_layers_;
   const bool greedy_;
   bool deep_ = false;
-  bool deep_mfma_ = false;    // deep trunk on the MFMA kernels (at 84x84)
+  bool deep_mfma_ = false;    // deep trunk on the MFMA kernels (at 84x84;
+                              // any supported size under resnet_any_)
   bool fused_heads_ = false;  // fused heads tail, else LSTM/ATen heads
   bool lstm_rows_ = false;    // LSTM serve kernels fit this model's core
   size_t head_base_ = 8;
