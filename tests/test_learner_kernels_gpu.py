@@ -28,7 +28,6 @@ independence of neighbouring rows, determinism, and greedy mode against
 first-index argmax with exact ties, with a grid tail and [T,B,A] input.
 """
 
-import functools
 import os
 import sys
 
@@ -46,6 +45,7 @@ else:  # pragma: no cover
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)),
                                 "helpers"))
 
+import heads_oracle as ho  # noqa: E402
 import loss_oracle as lso  # noqa: E402
 
 CPU_RATIO = 1.34  # measured: float32 eager CPU vs float64, see above
@@ -118,38 +118,13 @@ def test_fused_loss_cpu_float32_ratio_recorded():
 
 # ---- policy sampler ----
 
-N_DRAWS = 200_000
-A_FULL = 18
-DEAD = ((0, 17), (3, 9), (16, 17), (0, 1))  # the two -40 entries per vector
-
-
-@functools.lru_cache(maxsize=None)
-def _four_logit_vectors():
-    """Four different 18-action vectors: 16 live logits in [-0.9, 0.9], so
-    every live probability is at least e^-1.8/16 > 0.01, and two at -40."""
-    g = torch.Generator().manual_seed(40)
-    z = torch.rand(4, A_FULL, generator=g) * 1.8 - 0.9
-    for k, dead in enumerate(DEAD):
-        z[k, list(dead)] = -40.0
-    return z
-
-
-def _chi2_per_group(actions, z):
-    """Pearson chi-square over the 16 live cells of each of the four
-    interleaved groups, and the number of draws of dead cells."""
-    p = torch.softmax(z.double(), -1).numpy()
-    actions = actions.numpy()
-    stats, dead_draws = [], 0
-    for k in range(4):
-        counts = np.bincount(actions[k::4], minlength=A_FULL)
-        n = counts.sum()
-        live = [j for j in range(A_FULL) if j not in DEAD[k]]
-        dead_draws += int(counts[list(DEAD[k])].sum())
-        pk = p[k, live] / p[k, live].sum()  # dead mass is ~1e-17
-        expected = n * pk
-        assert expected.min() >= 500
-        stats.append(float(((counts[live] - expected) ** 2 / expected).sum()))
-    return stats, dead_draws
+# The logit vectors and the chi-square statistic are shared with the serve
+# plane's sampler tests (tests/test_serve_heads_gpu.py).
+N_DRAWS = ho.N_DRAWS
+A_FULL = ho.A_FULL
+DEAD = ho.DEAD  # the two -40 entries per vector
+_four_logit_vectors = ho.four_logit_vectors
+_chi2_per_group = ho.chi2_per_group
 
 
 def test_policy_sample_distribution_chi2():

@@ -305,6 +305,18 @@ PYBIND11_MODULE(_tbruntime, m) {
       py::arg("slab_base"), py::arg("slab_bytes"), py::arg("frame_addrs"),
       py::arg("reward_addrs"), py::arg("fsz"));
 
+  // ---- serve-plane heads and slot gather ----
+  // Test-only: heads_sample_kernel on caller-made tensors, in both core
+  // forms (rew = None: x alone), into caller-made pinned outputs.
+  m.def("heads_sample", &heads_sample, py::arg("x"), py::arg("rew"),
+        py::arg("policy_w"), py::arg("policy_b"), py::arg("base_w"),
+        py::arg("base_b"), py::arg("b"), py::arg("greedy"), py::arg("seed"),
+        py::arg("action"), py::arg("logits"), py::arg("baseline"));
+  // Test-only: gather_obs_kernel as the runner calls it.
+  m.def("gather_obs", &gather_obs, py::arg("slab_frames"),
+        py::arg("slab_rew"), py::arg("slab_done"), py::arg("ids"),
+        py::arg("bp"), py::arg("frame_shape"));
+
   // ---- LSTM serve step on state rows ----
   // Test-only: the layer kernels and the heads on caller-made tensors.
   m.def("lstm_serve_step", &lstm_serve_step, py::arg("x"), py::arg("rew"),

@@ -4,6 +4,7 @@
 
 #include <torch/extension.h>
 
+#include <optional>
 #include <tuple>
 #include <vector>
 
@@ -12,6 +13,14 @@
 
 namespace tbruntime {
 
+// Inference batch from slot ids (kernel comment in the .hip). The three slabs
+// are pinned host tensors over the same slots (frames uint8 [slots, ...] of
+// frame_shape, rewards float32, dones uint8), ids_cpu b int32 or int64 slot
+// ids on the CPU, 1 <= b <= bp. All of that, every id against the slot count
+// and the frame size against the 16-byte accesses, is checked (RuntimeError)
+// before anything is allocated or launched. Returns frames [bp, ...] uint8,
+// rew [bp, 1] clamped and nd [bp] = 1 - done on the GPU; rows >= b are zero
+// frames, reward 0, not-done 1. Bound as _tbruntime.gather_obs for the tests.
 std::vector<torch::Tensor> gather_obs(torch::Tensor slab_frames,
                                       torch::Tensor slab_rew,
                                       torch::Tensor slab_done,
@@ -39,7 +48,11 @@ void fused_heads_sample_out(const torch::Tensor& x, const torch::Tensor& rew,
 // The heads kernel over raw pointers. `core` is [>= b, D] f32 on the device;
 // with `rew` ([>= b] f32) the heads see [core, rew] (length D + 1), with
 // rew == nullptr the core alone (the recurrent tail: the last LSTM layer's
-// h). Same sampling code either way.
+// h). Same sampling code either way. Weights and biases are checked here
+// (contiguous f32 on the current GPU, [A, Dc] / A / [1, Dc] / 1 elements,
+// 1 <= A <= 64, the core within the LDS limit) and so is the launch's
+// result; the raw pointers are the caller's to vouch for, which
+// fused_heads_sample_out and heads_sample do for tensors.
 void launch_heads_sample(const float* core, const float* rew, int64_t D,
                          const torch::Tensor& policy_w,
                          const torch::Tensor& policy_b,
@@ -47,6 +60,18 @@ void launch_heads_sample(const float* core, const float* rew, int64_t D,
                          const torch::Tensor& base_b, int64_t b, bool greedy,
                          int64_t seed, int64_t* out_action, float* out_logits,
                          float* out_baseline);
+
+// Test surface: launch_heads_sample in either core form, [x, rew] or, with
+// rew = None, x alone, on caller-made tensors. action (int64), logits
+// ([n, A]) and baseline are pinned CPU tensors of at least b rows; rows >= b
+// are not written. The seed reaches the kernel unchanged (negative ones
+// too, as InferenceRunner::next_seed() makes them). Every argument is checked
+// (RuntimeError) before the launch; returns after the stream has run it.
+void heads_sample(torch::Tensor x, std::optional<torch::Tensor> rew,
+                  torch::Tensor policy_w, torch::Tensor policy_b,
+                  torch::Tensor base_w, torch::Tensor base_b, int64_t b,
+                  bool greedy, int64_t seed, torch::Tensor action,
+                  torch::Tensor logits, torch::Tensor baseline);
 
 // One LSTM layer's weights as lstm_serve_layer_kernel reads them (layout in
 // the kernel comment): w [4, Hn, Kp] bf16, bias [4, Hn] f32 = b_ih + b_hh.

@@ -144,8 +144,12 @@ __global__ __launch_bounds__(256) void heads_sample_kernel(
       hiprand_init(seed, s, 0, &rng);
       float bv = -1e30f;
       for (int a = 0; a < A; ++a) {
-        float u = hiprand_uniform(&rng);
-        u = u < 1e-20f ? 1e-20f : u;
+        // hiprand_uniform is (v + 1) * 2^-32 rounded to float: at least
+        // 2^-32, so the inner log is finite, but exactly 1.0f for the top
+        // ~2^7 values of v, where -log(-log(1)) = +inf would win against
+        // any logit. The largest float below 1 caps the Gumbel value at
+        // -log(-log(1 - 2^-24)) ~ 16.6 and changes no other draw.
+        const float u = fminf(hiprand_uniform(&rng), 0x1.fffffep-1f);
         const float g = s_logits[a] - __logf(-__logf(u));
         if (g > bv) {
           bv = g;
@@ -670,7 +674,55 @@ std::vector<torch::Tensor> gather_obs(torch::Tensor slab_frames,
                                       torch::Tensor slab_done,
                                       torch::Tensor ids_cpu, int64_t bp,
                                       std::vector<int64_t> frame_shape) {
-  const int b = ids_cpu.numel();
+  // Every check before any allocation or launch: the kernel reads the slabs
+  // in place over the host link, so a stray id, a pageable slab or a frame
+  // size the 16-byte accesses do not divide would be a GPU fault.
+  int64_t fsz = 1;
+  for (auto d : frame_shape) fsz *= d;
+  TORCH_CHECK(fsz >= 16 && fsz % 16 == 0 && fsz < (int64_t(1) << 31),
+              "gather_obs: frame bytes must be a multiple of 16 below 2^31, "
+              "got ", fsz);
+  const auto host_slab = [](const torch::Tensor& t, torch::ScalarType ty) {
+    return t.defined() && t.device().is_cpu() && t.scalar_type() == ty &&
+           t.is_contiguous() && t.is_pinned();
+  };
+  TORCH_CHECK(host_slab(slab_frames, torch::kUInt8) && slab_frames.dim() >= 1,
+              "gather_obs: frame slab must be a contiguous pinned uint8 CPU "
+              "tensor");
+  TORCH_CHECK(host_slab(slab_rew, torch::kFloat32),
+              "gather_obs: reward slab must be a contiguous pinned float32 "
+              "CPU tensor");
+  TORCH_CHECK(host_slab(slab_done, torch::kUInt8),
+              "gather_obs: done slab must be a contiguous pinned uint8 CPU "
+              "tensor");
+  const int64_t slots = slab_frames.size(0);
+  TORCH_CHECK(slots >= 1 && slab_rew.numel() == slots &&
+                  slab_done.numel() == slots,
+              "gather_obs: the slabs disagree on the slot count (",
+              slab_frames.size(0), " frames, ", slab_rew.numel(),
+              " rewards, ", slab_done.numel(), " dones)");
+  TORCH_CHECK(slab_frames.numel() == slots * fsz,
+              "gather_obs: frame_shape does not match the frame slab");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(slab_frames.data_ptr()) % 16 == 0,
+              "gather_obs: frame slab must be 16-byte aligned");
+  TORCH_CHECK(ids_cpu.defined() && ids_cpu.device().is_cpu() &&
+                  (ids_cpu.scalar_type() == torch::kInt32 ||
+                   ids_cpu.scalar_type() == torch::kInt64),
+              "gather_obs: ids must be an int32 or int64 CPU tensor");
+  const int64_t b = ids_cpu.numel();
+  TORCH_CHECK(b >= 1 && b <= bp && bp < (int64_t(1) << 31),
+              "gather_obs: need 1 <= b <= bp, got b = ", b, ", bp = ", bp);
+  {
+    const torch::Tensor flat = ids_cpu.reshape({-1});
+    const int64_t stride = flat.stride(0);
+    const bool wide = flat.scalar_type() == torch::kInt64;
+    for (int64_t r = 0; r < b; ++r) {
+      const int64_t id = wide ? flat.data_ptr<int64_t>()[r * stride]
+                              : (int64_t)flat.data_ptr<int32_t>()[r * stride];
+      TORCH_CHECK(id >= 0 && id < slots, "gather_obs: id ", id, " of request ",
+                  r, " is outside the slab's ", slots, " slots");
+    }
+  }
   auto dev = torch::Device(torch::kCUDA, at::cuda::current_device());
   auto opts = torch::TensorOptions().device(dev);
   // Pad the ids staging to the quantized batch size so the pinned-alloc
@@ -680,23 +732,83 @@ std::vector<torch::Tensor> gather_obs(torch::Tensor slab_frames,
                                         .pinned_memory(true));
   ids_pin.narrow(0, 0, b).copy_(ids_cpu.to(torch::kInt32).reshape({-1}));
   auto ids = ids_pin.to(dev, /*non_blocking=*/true);
-  int64_t fsz = 1;
-  for (auto d : frame_shape) fsz *= d;
   std::vector<int64_t> oshape = {bp};
   oshape.insert(oshape.end(), frame_shape.begin(), frame_shape.end());
   auto frames = torch::empty(oshape, opts.dtype(torch::kUInt8));
   auto rew = torch::empty({bp, 1}, opts.dtype(torch::kFloat32));
   auto nd = torch::empty({bp}, opts.dtype(torch::kFloat32));
-  TORCH_CHECK(fsz % 16 == 0, "frame bytes must be divisible by 16");
   hipLaunchKernelGGL(gather_obs_kernel, dim3((uint32_t)bp), dim3(256), 0,
                      at::cuda::getCurrentCUDAStream(),
                      slab_frames.data_ptr<uint8_t>(),
                      slab_rew.data_ptr<float>(),
                      slab_done.data_ptr<uint8_t>(), ids.data_ptr<int>(),
-                     b, (int)bp, (int)fsz, frames.data_ptr<uint8_t>(),
+                     (int)b, (int)bp, (int)fsz, frames.data_ptr<uint8_t>(),
                      rew.data_ptr<float>(), nd.data_ptr<float>());
+  const hipError_t err = hipGetLastError();
+  TORCH_CHECK(err == hipSuccess, "gather_obs launch: ",
+              hipGetErrorString(err));
   return {frames, rew, nd};
 }
+
+namespace {
+
+bool f32_on_gpu(const torch::Tensor& t) {
+  return t.defined() && t.is_cuda() && t.scalar_type() == torch::kFloat32 &&
+         t.is_contiguous();
+}
+
+// Host checks of the heads kernel's weights, for a core of Dc elements. The
+// kernel indexes all four by A and Dc alone, so a bias on the CPU or a short
+// one would be a GPU fault.
+void check_heads_weights(const torch::Tensor& policy_w,
+                         const torch::Tensor& policy_b,
+                         const torch::Tensor& base_w,
+                         const torch::Tensor& base_b, int64_t Dc) {
+  TORCH_CHECK(f32_on_gpu(policy_w) && f32_on_gpu(policy_b) &&
+                  f32_on_gpu(base_w) && f32_on_gpu(base_b),
+              "heads_sample: weights and biases must be contiguous float32 "
+              "GPU tensors");
+  TORCH_CHECK(policy_b.device() == policy_w.device() &&
+                  base_w.device() == policy_w.device() &&
+                  base_b.device() == policy_w.device() &&
+                  policy_w.device().index() == at::cuda::current_device(),
+              "heads_sample: weights and biases must be on the current GPU");
+  TORCH_CHECK(policy_w.dim() == 2 && base_w.dim() == 2,
+              "heads_sample: weights must be [A, Dc] and [1, Dc]");
+  const int64_t A = policy_w.size(0);
+  TORCH_CHECK(A >= 1 && A <= 64,
+              "heads_sample: 1 to 64 actions supported, got ", A);
+  TORCH_CHECK(Dc >= 1 && policy_w.size(1) == Dc && base_w.size(1) == Dc,
+              "heads_sample: head weights do not match the core's length ",
+              Dc);
+  TORCH_CHECK(base_w.size(0) == 1 && policy_b.numel() == A &&
+                  base_b.numel() == 1,
+              "heads_sample: need policy_b of A elements, base_w of one row "
+              "and base_b of one element");
+  // The core in dynamic LDS beside the kernel's 64 static floats.
+  const size_t limit = at::cuda::getCurrentDeviceProperties()->sharedMemPerBlock;
+  TORCH_CHECK((size_t)Dc * sizeof(float) + 64 * sizeof(float) <= limit,
+              "heads_sample: a core of ", Dc, " floats does not fit the ",
+              limit, " bytes of LDS");
+}
+
+// Host checks of the core as tensors: x [>= b, D], rew (if any) >= b
+// elements, both on the weights' GPU.
+void check_heads_inputs(const torch::Tensor& x, const torch::Tensor* rew,
+                        const torch::Tensor& policy_w, int64_t b) {
+  TORCH_CHECK(f32_on_gpu(x) && x.dim() == 2,
+              "heads_sample: x must be a contiguous float32 [n, D] GPU "
+              "tensor");
+  TORCH_CHECK(rew == nullptr || f32_on_gpu(*rew),
+              "heads_sample: rew must be a contiguous float32 GPU tensor");
+  TORCH_CHECK(policy_w.defined() && x.device() == policy_w.device() &&
+                  (rew == nullptr || rew->device() == x.device()),
+              "heads_sample: x, rew and the weights must be on one GPU");
+  TORCH_CHECK(b >= 1 && x.size(0) >= b && (rew == nullptr || rew->numel() >= b),
+              "heads_sample: batch of ", b, " exceeds its inputs");
+}
+
+}  // namespace
 
 // Writes action/logits/baseline into freshly allocated PINNED host tensors;
 // caller syncs the stream before reading them.
@@ -707,6 +819,9 @@ std::vector<torch::Tensor> fused_heads_sample(torch::Tensor x,
                                               torch::Tensor base_w,
                                               torch::Tensor base_b, int64_t b,
                                               bool greedy, int64_t seed) {
+  // Checked here too: nothing is allocated for a call that will not launch.
+  check_heads_inputs(x, &rew, policy_w, b);
+  check_heads_weights(policy_w, policy_b, base_w, base_b, x.size(1) + 1);
   const int A = policy_w.size(0);
   // Allocate pinned outputs at the quantized batch size (cache-friendly;
   // ragged sizes would hipHostMalloc + device-sync per serve), then hand
@@ -718,9 +833,10 @@ std::vector<torch::Tensor> fused_heads_sample(torch::Tensor x,
       torch::empty({bq, A}, hopts.dtype(torch::kFloat32)).narrow(0, 0, b);
   auto baseline =
       torch::empty({bq}, hopts.dtype(torch::kFloat32)).narrow(0, 0, b);
-  fused_heads_sample_out(x, rew, policy_w, policy_b, base_w, base_b, b, greedy,
-                         seed, action.data_ptr<int64_t>(),
-                         logits.data_ptr<float>(), baseline.data_ptr<float>());
+  launch_heads_sample(x.data_ptr<float>(), rew.data_ptr<float>(), x.size(1),
+                      policy_w, policy_b, base_w, base_b, b, greedy, seed,
+                      action.data_ptr<int64_t>(), logits.data_ptr<float>(),
+                      baseline.data_ptr<float>());
   return {action, logits, baseline};
 }
 
@@ -731,14 +847,10 @@ void fused_heads_sample_out(const torch::Tensor& x, const torch::Tensor& rew,
                             const torch::Tensor& base_b, int64_t b,
                             bool greedy, int64_t seed, int64_t* out_action,
                             float* out_logits, float* out_baseline) {
-  const int D = x.size(1);
-  TORCH_CHECK(policy_w.size(1) == D + 1 && base_w.size(1) == D + 1,
-              "head weights must take [x, reward]");
-  TORCH_CHECK(b >= 1 && x.size(0) >= b && rew.numel() >= b,
-              "heads kernel: batch exceeds its inputs");
-  launch_heads_sample(x.data_ptr<float>(), rew.data_ptr<float>(), D, policy_w,
-                      policy_b, base_w, base_b, b, greedy, seed, out_action,
-                      out_logits, out_baseline);
+  check_heads_inputs(x, &rew, policy_w, b);
+  launch_heads_sample(x.data_ptr<float>(), rew.data_ptr<float>(), x.size(1),
+                      policy_w, policy_b, base_w, base_b, b, greedy, seed,
+                      out_action, out_logits, out_baseline);
 }
 
 void launch_heads_sample(const float* core, const float* rew, int64_t D,
@@ -748,13 +860,15 @@ void launch_heads_sample(const float* core, const float* rew, int64_t D,
                          const torch::Tensor& base_b, int64_t b, bool greedy,
                          int64_t seed, int64_t* out_action, float* out_logits,
                          float* out_baseline) {
-  const int A = policy_w.size(0);
   const int64_t Dc = rew != nullptr ? D + 1 : D;
-  TORCH_CHECK(A <= 64, "heads kernel supports up to 64 actions");
-  TORCH_CHECK(policy_w.size(1) == Dc && base_w.size(1) == Dc &&
-                  policy_w.is_contiguous() && base_w.is_contiguous(),
-              "head weights do not match the core's length");
-  TORCH_CHECK(b >= 1 && core != nullptr, "heads kernel: empty batch");
+  TORCH_CHECK(D >= 1 && Dc < (int64_t(1) << 31),
+              "heads_sample: bad core length ", D);
+  check_heads_weights(policy_w, policy_b, base_w, base_b, Dc);
+  TORCH_CHECK(b >= 1 && b < (int64_t(1) << 31), "heads_sample: bad batch ", b);
+  TORCH_CHECK(core != nullptr && out_action != nullptr &&
+                  out_logits != nullptr && out_baseline != nullptr,
+              "heads_sample: null argument");
+  const int A = policy_w.size(0);
   const size_t lds = (size_t)Dc * sizeof(float);
   hipLaunchKernelGGL(heads_sample_kernel, dim3((uint32_t)b), dim3(256), lds,
                      at::cuda::getCurrentCUDAStream(), core, rew,
@@ -762,6 +876,43 @@ void launch_heads_sample(const float* core, const float* rew, int64_t D,
                      base_w.data_ptr<float>(), base_b.data_ptr<float>(),
                      (int)b, (int)D, A, (uint64_t)seed, greedy ? 1 : 0,
                      out_action, out_logits, out_baseline);
+  const hipError_t err = hipGetLastError();
+  TORCH_CHECK(err == hipSuccess, "heads_sample launch: ",
+              hipGetErrorString(err));
+}
+
+void heads_sample(torch::Tensor x, std::optional<torch::Tensor> rew,
+                  torch::Tensor policy_w, torch::Tensor policy_b,
+                  torch::Tensor base_w, torch::Tensor base_b, int64_t b,
+                  bool greedy, int64_t seed, torch::Tensor action,
+                  torch::Tensor logits, torch::Tensor baseline) {
+  const torch::Tensor* r = rew.has_value() ? &*rew : nullptr;
+  check_heads_inputs(x, r, policy_w, b);
+  at::cuda::CUDAGuard device_guard(x.device());
+  check_heads_weights(policy_w, policy_b, base_w, base_b,
+                      x.size(1) + (r != nullptr ? 1 : 0));
+  const int64_t A = policy_w.size(0);
+  const auto pinned = [](const torch::Tensor& t, torch::ScalarType ty) {
+    return t.defined() && t.device().is_cpu() && t.scalar_type() == ty &&
+           t.is_contiguous() && t.is_pinned();
+  };
+  TORCH_CHECK(pinned(action, torch::kInt64) && action.numel() >= b,
+              "heads_sample: action must be a contiguous pinned int64 CPU "
+              "tensor of at least b elements");
+  TORCH_CHECK(pinned(logits, torch::kFloat32) && logits.dim() == 2 &&
+                  logits.size(0) >= b && logits.size(1) == A,
+              "heads_sample: logits must be a contiguous pinned float32 CPU "
+              "tensor [>= b, A]");
+  TORCH_CHECK(pinned(baseline, torch::kFloat32) && baseline.numel() >= b,
+              "heads_sample: baseline must be a contiguous pinned float32 CPU "
+              "tensor of at least b elements");
+  launch_heads_sample(x.data_ptr<float>(),
+                      r != nullptr ? r->data_ptr<float>() : nullptr, x.size(1),
+                      policy_w, policy_b, base_w, base_b, b, greedy, seed,
+                      action.data_ptr<int64_t>(), logits.data_ptr<float>(),
+                      baseline.data_ptr<float>());
+  // The outputs are host memory the kernel writes over the link.
+  at::cuda::getCurrentCUDAStream().synchronize();
 }
 
 // ---- LSTM serve step ------------------------------------------------------
