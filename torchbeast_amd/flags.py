@@ -33,7 +33,20 @@ def add_common_flags(parser: argparse.ArgumentParser):
                              "MFMA conv kernels at frame sizes other than "
                              "84x84 (up to 256x256), in the learner and the "
                              "C++ runner; same as TBAMD_RESNET_ANY=1.")
+    parser.add_argument("--fc_mfma", action="store_true",
+                        help="Run the fully connected layer behind the conv "
+                             "trunk on the bf16 MFMA linear kernels, in the "
+                             "learner and the C++ runner; same as "
+                             "TBAMD_FC_MFMA=1.")
     return parser
+
+
+def apply_fc_mfma(flags):
+    """--fc_mfma -> TBAMD_FC_MFMA=1, which the models read at every forward
+    and the C++ runner at construction; call before either exists. Without
+    the flag the environment is left as it is."""
+    if getattr(flags, "fc_mfma", False):
+        os.environ["TBAMD_FC_MFMA"] = "1"
 
 
 def apply_resnet_any_geometry(flags):

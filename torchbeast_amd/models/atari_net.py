@@ -75,7 +75,9 @@ class AtariNet(nn.Module):
             x = F.relu(self.conv2(x))
             x = F.relu(self.conv3(x))
             x = x.view(T * B, -1)
-        x = F.relu(self.fc(x))
+        # TBAMD_FC_MFMA=1: the fc on the bf16 MFMA linear kernels.
+        y = tbf.fc_relu(self.fc, x)
+        x = F.relu(self.fc(x)) if y is None else y
 
         clipped_reward = torch.clamp(inputs["reward"], -1, 1).view(T * B, 1)
         if self.use_last_action:

@@ -155,7 +155,12 @@ class ResNet(nn.Module):
         x = self._features(x)
         # reshape (not view): the MFMA path returns channels_last; logical
         # NCHW flatten order is preserved either way.
-        x = F.relu(self.fc(F.relu(x).reshape(T * B, -1)))
+        x = F.relu(x).reshape(T * B, -1)
+        from torchbeast_amd.ops import functional as tbf
+
+        # TBAMD_FC_MFMA=1: the fc on the bf16 MFMA linear kernels.
+        y = tbf.fc_relu(self.fc, x)
+        x = F.relu(self.fc(x)) if y is None else y
 
         clipped_reward = torch.clamp(reward, -1, 1).view(T * B, 1)
         core_input = torch.cat([x, clipped_reward], dim=-1)

@@ -612,6 +612,58 @@ def resnet_conv3x3_supported(ci, hw, co):
 
 
 # ---------------------------------------------------------------------------
+# bf16 MFMA linear layer for the fc behind the trunks (linear_mfma.hip),
+# opt-in with TBAMD_FC_MFMA=1 (--fc_mfma).
+# ---------------------------------------------------------------------------
+
+
+class _LinearMfma(torch.autograd.Function):
+    """y = relu?(x @ W^T + b) on the MFMA linear kernels: bf16 operands
+    (rounded while staged), fp32 accumulation and outputs. The weight is
+    packed once per forward (it changes every learner step); backward runs
+    wgrad, and dgrad only when x needs a gradient."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, relu):
+        ext = _ext_for(x, "linear_fwd")
+        x = x.detach().contiguous()
+        wb, wt = ext.linear_pack(weight.detach().contiguous())
+        y = ext.linear_fwd(x, wb, bias.detach().contiguous(), relu)
+        ctx.save_for_backward(x, y, wt)
+        ctx.relu = relu
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, y, wt = ctx.saved_tensors
+        ext = ops_mod.require_ext()
+        dy = dy.contiguous()
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = ext.linear_dgrad(dy, y, wt, ctx.relu)
+        dw, db = ext.linear_wgrad(dy, y, x, ctx.relu)
+        return dx, dw, db, None
+
+
+def fc_relu(fc, x):
+    """relu(fc(x)) for an nn.Linear on the MFMA linear kernels, or None when
+    they do not apply (switch unset, CPU tensor, unsupported shape or dtype):
+    the caller then runs its eager line."""
+    if os.environ.get("TBAMD_FC_MFMA") != "1" or not x.is_cuda:
+        return None
+    if (x.dim() != 2 or x.dtype != torch.float32 or fc.bias is None
+            or fc.weight.dtype != torch.float32):
+        return None
+    ext = _ext_for(x, "linear_fwd")
+    if not ext.linear_supported(x.shape[0], fc.out_features, fc.in_features):
+        return None
+    x = x.contiguous()
+    if x.data_ptr() % 16 or fc.weight.data_ptr() % 16:
+        return None  # the kernels move rows as 16 B vectors
+    return _LinearMfma.apply(x, fc.weight, fc.bias, True)
+
+
+# ---------------------------------------------------------------------------
 # Policy sampling: softmax + multinomial (train) / argmax (eval).
 # ---------------------------------------------------------------------------
 

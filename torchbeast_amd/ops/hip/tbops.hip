@@ -29,6 +29,7 @@
 
 #include "atari_trunk.h"
 #include "conv_mfma.h"
+#include "linear_mfma.h"
 
 namespace tbamd {
 std::vector<double> barrier_probe(int64_t variant, int64_t wgs, int64_t iters);
@@ -787,6 +788,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("resnet_conv_any", &tbamd::resnet_conv_any);
   m.def("resnet_conv_any_supported", &tbamd::resnet_conv_any_supported);
   m.def("resnet_conv_any_wgrad", &tbamd::resnet_conv_any_wgrad);
+  m.def("linear_supported", &tbamd::linear_supported);
+  m.def("linear_pack", &tbamd::linear_pack);
+  m.def("linear_fwd", &tbamd::linear_fwd);
+  m.def("linear_dgrad", &tbamd::linear_dgrad);
+  m.def("linear_wgrad", &tbamd::linear_wgrad);
   m.def("barrier_probe", &tbamd::barrier_probe);
   m.def("launch_probe", &tbamd::launch_probe);
   m.def("mfma_gemm", &tbamd::mfma_gemm);

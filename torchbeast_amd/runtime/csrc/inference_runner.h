@@ -14,7 +14,8 @@
 //           (inputs_from_slots); tensors, cat-ed on the host by the batcher,
 //           then H2D (inputs_from_tensors).
 //   trunk   frames -> conv features -> fc: hand-written MFMA or fused conv
-//           kernels, ATen/MIOpen for the rest. bf16 weight packs are cached
+//           kernels, ATen/MIOpen for the rest (the fc too, unless
+//           TBAMD_FC_MFMA=1 puts it on linear_mfma.hip). bf16 weight packs are cached
 //           until mark_weights_dirty().
 //   tail    heads, the batch's one stream synchronise, delivery: fused heads
 //           scattered into the rows (tail_fused_rows) or into pinned tensors
@@ -42,6 +43,7 @@
 
 #include "../../ops/hip/atari_trunk.h"
 #include "../../ops/hip/conv_mfma.h"
+#include "../../ops/hip/linear_mfma.h"
 #include "queues.h"
 #include "runtime_kernels.h"
 
@@ -611,8 +613,30 @@ class InferenceRunner {
       x = at::conv2d(x, weights_[4], weights_[5], 1).relu_();
       x = x.reshape({bp, -1});
     }
-    return at::linear(x, weights_[head_base_ - 2], weights_[head_base_ - 1])
-        .relu_();
+    const torch::Tensor& fc_w = weights_[head_base_ - 2];
+    if (fc_mfma_ && x.scalar_type() == torch::kFloat32 &&
+        fc_w.scalar_type() == torch::kFloat32 && fc_w.is_contiguous() &&
+        reinterpret_cast<uintptr_t>(fc_w.data_ptr()) % 16 == 0 &&
+        tbamd::linear_supported(x.size(0), fc_w.size(0), fc_w.size(1))) {
+      // TBAMD_FC_MFMA=1: the fc on the bf16 MFMA linear kernels, from the
+      // cached [N, K] pack.
+      return tbamd::linear_fwd(x.contiguous(), fc_pack(stream),
+                               weights_[head_base_ - 1].contiguous(),
+                               /*relu=*/true);
+    }
+    return at::linear(x, fc_w, weights_[head_base_ - 1]).relu_();
+  }
+
+  // bf16 pack of the fc weight, cached like packed_weights().
+  torch::Tensor fc_pack(at::cuda::CUDAStream& stream) {
+    std::lock_guard<std::mutex> g(pack_mu_);
+    const int64_t v = weights_version_.load();
+    if (fc_packed_version_ != v) {
+      fc_packed_ = tbamd::linear_pack(weights_[head_base_ - 2])[0];
+      stream.synchronize();
+      fc_packed_version_ = v;
+    }
+    return fc_packed_;
   }
 
   // bf16 channels_last ResNet trunk, every conv on the MFMA template.
@@ -981,6 +1005,8 @@ class InferenceRunner {
   std::mutex pack_mu_;
   std::vector<torch::Tensor> packed_;  // see packed_weights
   int64_t packed_version_ = -1;
+  torch::Tensor fc_packed_;  // see fc_pack
+  int64_t fc_packed_version_ = -1;
   std::atomic<int64_t> weights_version_{0};
   std::atomic<uint64_t> seed_ctr_{1};
   // Benchmarking: serve everything through library ops (the strategy
@@ -990,6 +1016,12 @@ class InferenceRunner {
   const bool resnet_any_ = [] {
     const char* v = std::getenv("TBAMD_RESNET_ANY");
     return v != nullptr && v[0] == '1' && v[1] == '\0';
+  }();
+  // TBAMD_FC_MFMA=1: the fc on the MFMA linear kernels (linear_mfma.hip).
+  const bool fc_mfma_ = [] {
+    const char* v = std::getenv("TBAMD_FC_MFMA");
+    return v != nullptr && v[0] == '1' && v[1] == '\0' &&
+           std::getenv("TBAMD_RUNNER_ATEN") == nullptr;
   }();
   const bool serve_timing_ = std::getenv("TBAMD_SERVE_TIMINGS") != nullptr;
   const bool trace_ = std::getenv("TBAMD_SERVE_TRACE") != nullptr;
