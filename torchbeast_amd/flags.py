@@ -38,7 +38,18 @@ def add_common_flags(parser: argparse.ArgumentParser):
                              "trunk on the bf16 MFMA linear kernels, in the "
                              "learner and the C++ runner; same as "
                              "TBAMD_FC_MFMA=1.")
+    parser.add_argument("--heads_mfma", action="store_true",
+                        help="Run the learner's policy and baseline heads on "
+                             "the fp32 MFMA heads kernels; same as "
+                             "TBAMD_HEADS_MFMA=1.")
     return parser
+
+
+def apply_heads_mfma(flags):
+    """--heads_mfma -> TBAMD_HEADS_MFMA=1, which the models read at every
+    forward. Without the flag the environment is left as it is."""
+    if getattr(flags, "heads_mfma", False):
+        os.environ["TBAMD_HEADS_MFMA"] = "1"
 
 
 def apply_fc_mfma(flags):

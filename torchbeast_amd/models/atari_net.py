@@ -61,24 +61,8 @@ class AtariNet(nn.Module):
             for _ in range(2)
         )
 
-    def forward(self, inputs, core_state=()):
-        from torchbeast_amd.ops import functional as tbf
-
-        frame = inputs["frame"]  # [T, B, C, H, W], uint8.
-        T, B = frame.shape[:2]
-        flat_frames = torch.flatten(frame, 0, 1)
-        # GPU: fused u8 conv trunk (one kernel); CPU/oversized: eager chain.
-        x = tbf.atari_trunk(flat_frames, self.conv1, self.conv2, self.conv3)
-        if x is None:
-            x = flat_frames.float() / 255.0
-            x = F.relu(self.conv1(x))
-            x = F.relu(self.conv2(x))
-            x = F.relu(self.conv3(x))
-            x = x.view(T * B, -1)
-        # TBAMD_FC_MFMA=1: the fc on the bf16 MFMA linear kernels.
-        y = tbf.fc_relu(self.fc, x)
-        x = F.relu(self.fc(x)) if y is None else y
-
+    def _core(self, inputs, x, core_state, T, B):
+        """(core_output [T*B, core_size], core_state) from the fc output."""
         clipped_reward = torch.clamp(inputs["reward"], -1, 1).view(T * B, 1)
         if self.use_last_action:
             last_action = torch.flatten(inputs["last_action"], 0, 1)
@@ -100,11 +84,44 @@ class AtariNet(nn.Module):
             core_output = torch.flatten(core_output_seq, 0, 1)
         else:
             core_output = core_input
+        return core_output, core_state
 
-        policy_logits = self.policy(core_output)
-        baseline = self.baseline(core_output)
-
+    def forward(self, inputs, core_state=()):
         from torchbeast_amd.ops import functional as tbf
+
+        frame = inputs["frame"]  # [T, B, C, H, W], uint8.
+        T, B = frame.shape[:2]
+        flat_frames = torch.flatten(frame, 0, 1)
+        # GPU: fused u8 conv trunk (one kernel); CPU/oversized: eager chain.
+        x = tbf.atari_trunk(flat_frames, self.conv1, self.conv2, self.conv3)
+        if x is None:
+            x = flat_frames.float() / 255.0
+            x = F.relu(self.conv1(x))
+            x = F.relu(self.conv2(x))
+            x = F.relu(self.conv3(x))
+            x = x.view(T * B, -1)
+        # TBAMD_FC_MFMA=1: the fc on the bf16 MFMA linear kernels.
+        y = tbf.fc_relu(self.fc, x)
+        x = F.relu(self.fc(x)) if y is None else y
+
+        # TBAMD_HEADS_MFMA=1: both heads on the fp32 MFMA heads kernels. With
+        # no LSTM they compose the core input themselves, from x, the reward
+        # and the last action; it is then never built.
+        heads_out = None
+        if not self.use_lstm:
+            heads_out = tbf.heads(
+                self.policy, self.baseline, x, inputs["reward"].reshape(-1),
+                torch.flatten(inputs["last_action"], 0, 1)
+                if self.use_last_action else None)
+        if heads_out is None:
+            core_output, core_state = self._core(inputs, x, core_state, T, B)
+            if self.use_lstm:  # the LSTM output, in the plain form
+                heads_out = tbf.heads(self.policy, self.baseline, core_output)
+        if heads_out is None:
+            policy_logits = self.policy(core_output)
+            baseline = self.baseline(core_output)
+        else:
+            policy_logits, baseline = heads_out
 
         action = tbf.policy_sample(policy_logits, greedy=not self.training)
 

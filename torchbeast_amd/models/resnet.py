@@ -162,25 +162,33 @@ class ResNet(nn.Module):
         y = tbf.fc_relu(self.fc, x)
         x = F.relu(self.fc(x)) if y is None else y
 
-        clipped_reward = torch.clamp(reward, -1, 1).view(T * B, 1)
-        core_input = torch.cat([x, clipped_reward], dim=-1)
+        # TBAMD_HEADS_MFMA=1: both heads on the fp32 MFMA heads kernels. With
+        # no LSTM they compose [x | clipped reward] themselves; it is then
+        # never built.
+        heads_out = None
+        if not self.use_lstm:
+            heads_out = tbf.heads(self.policy, self.baseline, x,
+                                  reward.reshape(-1))
+        if heads_out is None:
+            clipped_reward = torch.clamp(reward, -1, 1).view(T * B, 1)
+            core_input = torch.cat([x, clipped_reward], dim=-1)
 
-        if self.use_lstm:
-            from torchbeast_amd.ops import functional as tbf
-
-            core_input = core_input.view(T, B, -1)
-            notdone = (~done).float()
-            core_output_seq, core_state = tbf.lstm_unroll(
-                self.core, core_input, notdone, core_state
-            )
-            core_output = torch.flatten(core_output_seq, 0, 1)
+            if self.use_lstm:
+                core_input = core_input.view(T, B, -1)
+                notdone = (~done).float()
+                core_output_seq, core_state = tbf.lstm_unroll(
+                    self.core, core_input, notdone, core_state
+                )
+                core_output = torch.flatten(core_output_seq, 0, 1)
+                # The LSTM output, in the plain form.
+                heads_out = tbf.heads(self.policy, self.baseline, core_output)
+            else:
+                core_output = core_input
+        if heads_out is None:
+            policy_logits = self.policy(core_output)
+            baseline = self.baseline(core_output)
         else:
-            core_output = core_input
-
-        policy_logits = self.policy(core_output)
-        baseline = self.baseline(core_output)
-
-        from torchbeast_amd.ops import functional as tbf
+            policy_logits, baseline = heads_out
 
         action = tbf.policy_sample(policy_logits, greedy=not self.training)
 

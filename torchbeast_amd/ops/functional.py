@@ -664,6 +664,78 @@ def fc_relu(fc, x):
 
 
 # ---------------------------------------------------------------------------
+# fp32 MFMA policy and baseline heads of the learner (heads_mfma.hip),
+# opt-in with TBAMD_HEADS_MFMA=1 (--heads_mfma).
+# ---------------------------------------------------------------------------
+
+
+class _HeadsMfma(torch.autograd.Function):
+    """(logits [M, A], baseline [M]) from the virtual core input
+    [x | clamp(reward, -1, 1) | one_hot(last_action)] (reward and last_action
+    optional), fp32 throughout. A gradient that autograd leaves out for one
+    output is passed to the kernels as a missing operand."""
+
+    @staticmethod
+    def forward(ctx, x, reward, last_action, pw, pb, bw, bb):
+        ext = _ext_for(x, "heads_fwd")
+        x = x.detach().contiguous()
+        pw, bw = pw.detach().contiguous(), bw.detach().contiguous()
+        logits, baseline = ext.heads_fwd(
+            x, reward, last_action, pw, pb.detach().contiguous(), bw,
+            bb.detach().contiguous())
+        ctx.save_for_backward(x, reward, last_action, pw, bw)
+        ctx.set_materialize_grads(False)
+        return logits, baseline
+
+    @staticmethod
+    def backward(ctx, dlogits, dbaseline):
+        x, reward, last_action, pw, bw = ctx.saved_tensors
+        if dlogits is None and dbaseline is None:
+            return (None,) * 7
+        ext = ops_mod.require_ext()
+        dlogits = None if dlogits is None else dlogits.contiguous()
+        dbaseline = None if dbaseline is None else dbaseline.contiguous()
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = ext.heads_dgrad(dlogits, dbaseline, pw, bw, x.shape[1])
+        dpw, dpb, dbw, dbb = ext.heads_wgrad(
+            x, reward, last_action, dlogits, dbaseline, pw.shape[0])
+        return dx, None, None, dpw, dpb, dbw, dbb
+
+
+def heads(policy, baseline, x, reward=None, last_action=None):
+    """(policy_logits [M, A], baseline [M]) of the two head nn.Linears on the
+    fp32 MFMA heads kernels, or None when they do not apply (switch unset,
+    CPU tensor, unsupported shape or dtype): the caller then runs its eager
+    lines. With reward [M] (and last_action [M]) the core input
+    [x | clamp(reward, -1, 1) | one_hot(last_action)] is never built."""
+    if os.environ.get("TBAMD_HEADS_MFMA") != "1" or not x.is_cuda:
+        return None
+    if (x.dim() != 2 or x.dtype != torch.float32
+            or policy.weight.dtype != torch.float32
+            or policy.bias is None or baseline.bias is None
+            or baseline.out_features != 1
+            or (reward is None and last_action is not None)
+            or (reward is not None and reward.dtype != torch.float32)
+            or (last_action is not None
+                and last_action.dtype not in (torch.int64, torch.int32))):
+        return None
+    ext = _ext_for(x, "heads_fwd")
+    extra = policy.in_features - x.shape[1]
+    want = (reward is not None) + (
+        policy.out_features if last_action is not None else 0)
+    if (x.shape[0] < 1 or extra != want or not ext.heads_supported(
+            x.shape[1], extra, policy.out_features)):
+        return None
+    if reward is not None:
+        reward = reward.detach().contiguous()
+    if last_action is not None:
+        last_action = last_action.contiguous()
+    return _HeadsMfma.apply(x, reward, last_action, policy.weight,
+                            policy.bias, baseline.weight, baseline.bias)
+
+
+# ---------------------------------------------------------------------------
 # Policy sampling: softmax + multinomial (train) / argmax (eval).
 # ---------------------------------------------------------------------------
 

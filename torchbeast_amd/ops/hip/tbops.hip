@@ -29,6 +29,7 @@
 
 #include "atari_trunk.h"
 #include "conv_mfma.h"
+#include "heads_mfma.h"
 #include "linear_mfma.h"
 
 namespace tbamd {
@@ -793,6 +794,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("linear_fwd", &tbamd::linear_fwd);
   m.def("linear_dgrad", &tbamd::linear_dgrad);
   m.def("linear_wgrad", &tbamd::linear_wgrad);
+  m.def("heads_supported", &tbamd::heads_supported);
+  m.def("heads_fwd", &tbamd::heads_fwd);
+  m.def("heads_dgrad", &tbamd::heads_dgrad);
+  m.def("heads_wgrad", &tbamd::heads_wgrad, py::arg("x"), py::arg("reward"),
+        py::arg("last_action"), py::arg("dlogits"), py::arg("dbaseline"),
+        py::arg("num_actions") = -1);
   m.def("barrier_probe", &tbamd::barrier_probe);
   m.def("launch_probe", &tbamd::launch_probe);
   m.def("mfma_gemm", &tbamd::mfma_gemm);
