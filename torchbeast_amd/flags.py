@@ -42,6 +42,10 @@ def add_common_flags(parser: argparse.ArgumentParser):
                         help="Run the learner's policy and baseline heads on "
                              "the fp32 MFMA heads kernels; same as "
                              "TBAMD_HEADS_MFMA=1.")
+    parser.add_argument("--lstm_mfma", action="store_true",
+                        help="Run the learner LSTM's input projection and its "
+                             "input and weight gradients on the bf16 MFMA "
+                             "projection kernels; same as TBAMD_LSTM_MFMA=1.")
     return parser
 
 
@@ -50,6 +54,13 @@ def apply_heads_mfma(flags):
     forward. Without the flag the environment is left as it is."""
     if getattr(flags, "heads_mfma", False):
         os.environ["TBAMD_HEADS_MFMA"] = "1"
+
+
+def apply_lstm_mfma(flags):
+    """--lstm_mfma -> TBAMD_LSTM_MFMA=1, which lstm_unroll reads at every
+    forward. Without the flag the environment is left as it is."""
+    if getattr(flags, "lstm_mfma", False):
+        os.environ["TBAMD_LSTM_MFMA"] = "1"
 
 
 def apply_fc_mfma(flags):

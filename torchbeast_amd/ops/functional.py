@@ -210,20 +210,25 @@ def fused_impala_loss(logits, baseline, actions, pg_advantages, vs):
 
 class _LstmUnroll(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, notdone, h0, c0, *flat_weights):
+    def forward(ctx, proj_mfma, x, notdone, h0, c0, *flat_weights):
         ext = _ext_for(x, "lstm_unroll_fwd")
         num_layers = len(flat_weights) // 4
-        results = ext.lstm_unroll_fwd(
+        args = (
             x.contiguous(),
             notdone.contiguous(),
             h0.contiguous(),
             c0.contiguous(),
             [w.contiguous() for w in flat_weights],
         )
+        # TBAMD_LSTM_MFMA=1: the input projection on lstm_proj_mfma.hip.
+        results = (ext.lstm_unroll_fwd(*args, True) if proj_mfma
+                   else ext.lstm_unroll_fwd(*args))
         out, hT, cT = results[:3]
-        stash = results[3:]  # Per layer: input, gates, hm, cm, c.
+        # Per layer: input, gates, hm, cm, c (and the wt pack if proj_mfma).
+        stash = results[3:]
         ctx.save_for_backward(notdone, h0, c0, *flat_weights, *stash)
         ctx.num_layers = num_layers
+        ctx.proj_mfma = proj_mfma
         return out, hT, cT
 
     @staticmethod
@@ -234,7 +239,7 @@ class _LstmUnroll(torch.autograd.Function):
         flat_weights = list(saved[3 : 3 + nw])
         stash = list(saved[3 + nw :])
         ext = ops_mod.require_ext()
-        grads = ext.lstm_unroll_bwd(
+        args = (
             notdone,
             h0,
             c0,
@@ -244,9 +249,27 @@ class _LstmUnroll(torch.autograd.Function):
             d_hT.contiguous(),
             d_cT.contiguous(),
         )
+        grads = (ext.lstm_unroll_bwd(*args, True) if ctx.proj_mfma
+                 else ext.lstm_unroll_bwd(*args))
         d_x, d_h0, d_c0 = grads[:3]
         d_weights = grads[3:]
-        return (d_x, None, d_h0, d_c0, *d_weights)
+        return (None, d_x, None, d_h0, d_c0, *d_weights)
+
+
+def _lstm_proj_mfma(core, x, state):
+    """TBAMD_LSTM_MFMA=1 (--lstm_mfma), fp32 on the GPU and every layer's
+    shape accepted by the planner; unset, no lstm_proj_* symbol is touched."""
+    if os.environ.get("TBAMD_LSTM_MFMA") != "1":
+        return False
+    if x.dtype != torch.float32 or state[0].dtype != torch.float32:
+        return False
+    ext = _ext_for(x, "lstm_proj_fwd")
+    rows, hidden = x.shape[0] * x.shape[1], core.hidden_size
+    return all(
+        getattr(core, f"weight_ih_l{layer}").dtype == torch.float32
+        and ext.lstm_proj_supported(
+            rows, core.input_size if layer == 0 else hidden, hidden)
+        for layer in range(core.num_layers))
 
 
 def lstm_unroll(core, x, notdone, state):
@@ -265,7 +288,8 @@ def lstm_unroll(core, x, notdone, state):
                 getattr(core, f"bias_ih_l{layer}"),
                 getattr(core, f"bias_hh_l{layer}"),
             ]
-        out, hT, cT = _LstmUnroll.apply(x, notdone, state[0], state[1], *flat)
+        out, hT, cT = _LstmUnroll.apply(_lstm_proj_mfma(core, x, state), x,
+                                        notdone, state[0], state[1], *flat)
         return out, (hT, cT)
 
     outputs = []

@@ -31,6 +31,7 @@
 #include "conv_mfma.h"
 #include "heads_mfma.h"
 #include "linear_mfma.h"
+#include "lstm_proj_mfma.h"
 
 namespace tbamd {
 std::vector<double> barrier_probe(int64_t variant, int64_t wgs, int64_t iters);
@@ -656,9 +657,13 @@ void lstm4_bwd_launch(torch::Tensor gates, torch::Tensor cm,
 }  // namespace tbamd
 
 // Multi-layer forward. flat_weights: [w_ih, w_hh, b_ih, b_hh] per layer.
+// proj_mfma: the input projection on the bf16 MFMA kernels of
+// lstm_proj_mfma.hip; the stash then carries the [I, Np] weight pack as a
+// sixth entry per layer.
 std::vector<torch::Tensor> lstm_unroll_fwd(
     torch::Tensor x, torch::Tensor notdone, torch::Tensor h0,
-    torch::Tensor c0, std::vector<torch::Tensor> flat_weights) {
+    torch::Tensor c0, std::vector<torch::Tensor> flat_weights,
+    bool proj_mfma = false) {
   TORCH_CHECK(x.is_cuda() && x.dim() == 3, "lstm: x must be [T,B,I] on GPU");
   const int T = x.size(0);
   const int B = x.size(1);
@@ -671,21 +676,33 @@ std::vector<torch::Tensor> lstm_unroll_fwd(
   auto hT = torch::empty({L, B, H}, opts);
   auto cT = torch::empty({L, B, H}, opts);
 
-  std::vector<torch::Tensor> stash;  // per layer: input, gates, hm, cm, c
+  // per layer: input, gates, hm, cm, c (and wt when proj_mfma)
+  std::vector<torch::Tensor> stash;
   torch::Tensor layer_in = x.contiguous();
   torch::Tensor out;
 
   for (int l = 0; l < L; ++l) {
     auto w_ih = flat_weights[4 * l].contiguous();
     auto w_hh = flat_weights[4 * l + 1].contiguous();
-    auto bias = (flat_weights[4 * l + 2] + flat_weights[4 * l + 3]);
 
     // The parallel 90%: one GEMM over all T*B rows.
-    auto precomp =
-        (torch::matmul(layer_in.reshape({(int64_t)T * B, -1}), w_ih.t()) +
-         bias)
-            .reshape({T, B, 4 * H})
-            .contiguous();
+    torch::Tensor precomp, wt;
+    if (proj_mfma) {
+      auto packs = tbamd::lstm_proj_pack(w_ih);
+      wt = packs[1];
+      precomp = tbamd::lstm_proj_fwd(
+                    layer_in.reshape({(int64_t)T * B, -1}), packs[0],
+                    flat_weights[4 * l + 2].contiguous(),
+                    flat_weights[4 * l + 3].contiguous())
+                    .view({T, B, 4 * H});
+    } else {
+      auto bias = (flat_weights[4 * l + 2] + flat_weights[4 * l + 3]);
+      precomp =
+          (torch::matmul(layer_in.reshape({(int64_t)T * B, -1}), w_ih.t()) +
+           bias)
+              .reshape({T, B, 4 * H})
+              .contiguous();
+    }
 
     out = torch::empty({T, B, H}, opts);
     auto gates = torch::empty({T, B, 4 * H}, opts);
@@ -704,6 +721,7 @@ std::vector<torch::Tensor> lstm_unroll_fwd(
     stash.push_back(hm);
     stash.push_back(cm);
     stash.push_back(c_out);
+    if (proj_mfma) stash.push_back(wt);
     layer_in = out;
   }
 
@@ -716,8 +734,11 @@ std::vector<torch::Tensor> lstm_unroll_bwd(
     torch::Tensor notdone, torch::Tensor h0, torch::Tensor c0,
     std::vector<torch::Tensor> flat_weights,
     std::vector<torch::Tensor> stash, torch::Tensor d_out_top,
-    torch::Tensor d_hT, torch::Tensor d_cT) {
+    torch::Tensor d_hT, torch::Tensor d_cT, bool proj_mfma = false) {
   const int L = flat_weights.size() / 4;
+  const int per_layer = proj_mfma ? 6 : 5;
+  TORCH_CHECK((int)stash.size() == per_layer * L, "lstm_unroll_bwd: stash of ",
+              stash.size(), " tensors, want ", per_layer, " per layer");
   const int T = d_out_top.size(0);
   const int B = d_out_top.size(1);
   const int H = h0.size(2);
@@ -731,11 +752,11 @@ std::vector<torch::Tensor> lstm_unroll_bwd(
 
   torch::Tensor d_out = d_out_top.contiguous();
   for (int l = L - 1; l >= 0; --l) {
-    auto layer_in = stash[5 * l];
-    auto gates = stash[5 * l + 1];
-    auto hm = stash[5 * l + 2];
-    auto cm = stash[5 * l + 3];
-    auto c_out = stash[5 * l + 4];
+    auto layer_in = stash[per_layer * l];
+    auto gates = stash[per_layer * l + 1];
+    auto hm = stash[per_layer * l + 2];
+    auto cm = stash[per_layer * l + 3];
+    auto c_out = stash[per_layer * l + 4];
     auto w_ih = flat_weights[4 * l].contiguous();
     auto w_hh = flat_weights[4 * l + 1].contiguous();
     auto w_hh_t_bf =
@@ -753,6 +774,19 @@ std::vector<torch::Tensor> lstm_unroll_bwd(
     auto dg2 = dgates.reshape({(int64_t)T * B, 4 * H});
     auto in2 = layer_in.reshape({(int64_t)T * B, -1});
     auto hm2 = hm.reshape({(int64_t)T * B, H});
+    if (proj_mfma) {
+      auto g = tbamd::lstm_proj_wgrad(dg2, in2, hm2);
+      d_weights[4 * l] = g[0];      // dW_ih
+      d_weights[4 * l + 1] = g[1];  // dW_hh
+      d_weights[4 * l + 2] = g[2];  // db_ih
+      d_weights[4 * l + 3] = g[2];  // db_hh: the same sums
+      d_h0[l] = dh;
+      d_c0[l] = dc;
+      d_out = tbamd::lstm_proj_dgrad(dg2, stash[per_layer * l + 5],
+                                     in2.size(1))
+                  .view({T, B, -1});
+      continue;
+    }
     d_weights[4 * l] = torch::matmul(dg2.t(), in2);       // dW_ih
     d_weights[4 * l + 1] = torch::matmul(dg2.t(), hm2);   // dW_hh
     auto db = dg2.sum(0);
@@ -794,6 +828,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("linear_fwd", &tbamd::linear_fwd);
   m.def("linear_dgrad", &tbamd::linear_dgrad);
   m.def("linear_wgrad", &tbamd::linear_wgrad);
+  m.def("lstm_proj_supported", &tbamd::lstm_proj_supported);
+  m.def("lstm_proj_pack", &tbamd::lstm_proj_pack);
+  m.def("lstm_proj_fwd", &tbamd::lstm_proj_fwd);
+  m.def("lstm_proj_dgrad", &tbamd::lstm_proj_dgrad);
+  m.def("lstm_proj_wgrad", &tbamd::lstm_proj_wgrad);
   m.def("heads_supported", &tbamd::heads_supported);
   m.def("heads_fwd", &tbamd::heads_fwd);
   m.def("heads_dgrad", &tbamd::heads_dgrad);
@@ -822,6 +861,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("momentum_buf") = std::nullopt,
         py::arg("grad_avg") = std::nullopt, py::arg("momentum") = 0.0);
   m.def("policy_sample", &policy_sample);
-  m.def("lstm_unroll_fwd", &lstm_unroll_fwd);
-  m.def("lstm_unroll_bwd", &lstm_unroll_bwd);
+  m.def("lstm_unroll_fwd", &lstm_unroll_fwd, py::arg("x"), py::arg("notdone"),
+        py::arg("h0"), py::arg("c0"), py::arg("flat_weights"),
+        py::arg("proj_mfma") = false);
+  m.def("lstm_unroll_bwd", &lstm_unroll_bwd, py::arg("notdone"), py::arg("h0"),
+        py::arg("c0"), py::arg("flat_weights"), py::arg("stash"),
+        py::arg("d_out_top"), py::arg("d_hT"), py::arg("d_cT"),
+        py::arg("proj_mfma") = false);
 }
