@@ -43,6 +43,28 @@ print(f"T={T} B={B} H={H} L={L}")
 print(f"lstm fwd      : {timed(fwd):8.3f} ms")
 print(f"lstm fwd+bwd  : {timed(fwd_bwd):8.3f} ms")
 
+# lstm4 next to the persistent MFMA kernels (TBAMD_LSTM_GATE_MFMA=1), in this
+# process, alternating; lstm_unroll reads the switch at every forward.
+def switched(fn, on):
+    def run():
+        if on:
+            os.environ["TBAMD_LSTM_GATE_MFMA"] = "1"
+        else:
+            os.environ.pop("TBAMD_LSTM_GATE_MFMA", None)
+        fn()
+    return run
+
+rows = {(n, on): [] for n in ("fwd", "fwd+bwd") for on in (False, True)}
+for _ in range(5):
+    for (n, on), acc in rows.items():
+        acc.append(timed(switched(fwd if n == "fwd" else fwd_bwd, on),
+                         iters=10, warmup=2))
+os.environ.pop("TBAMD_LSTM_GATE_MFMA", None)
+for (n, on), acc in rows.items():
+    acc.sort()
+    print(f"{'gate-mfma' if on else 'lstm4    '} {n:8s}: median "
+          f"{acc[len(acc) // 2]:8.3f} ms  [{acc[0]:.3f} .. {acc[-1]:.3f}]")
+
 # Eager torch baseline (cuDNN-style per-step loop, masked).
 def eager():
     state = (h0, c0)

@@ -46,6 +46,10 @@ def add_common_flags(parser: argparse.ArgumentParser):
                         help="Run the learner LSTM's input projection and its "
                              "input and weight gradients on the bf16 MFMA "
                              "projection kernels; same as TBAMD_LSTM_MFMA=1.")
+    parser.add_argument("--lstm_gate_mfma", action="store_true",
+                        help="Run the learner LSTM's recurrence (forward and "
+                             "backward over time) on the persistent bf16 MFMA "
+                             "gate kernels; same as TBAMD_LSTM_GATE_MFMA=1.")
     return parser
 
 
@@ -61,6 +65,13 @@ def apply_lstm_mfma(flags):
     forward. Without the flag the environment is left as it is."""
     if getattr(flags, "lstm_mfma", False):
         os.environ["TBAMD_LSTM_MFMA"] = "1"
+
+
+def apply_lstm_gate_mfma(flags):
+    """--lstm_gate_mfma -> TBAMD_LSTM_GATE_MFMA=1, which lstm_unroll reads at
+    every forward. Without the flag the environment is left as it is."""
+    if getattr(flags, "lstm_gate_mfma", False):
+        os.environ["TBAMD_LSTM_GATE_MFMA"] = "1"
 
 
 def apply_fc_mfma(flags):

@@ -210,7 +210,7 @@ def fused_impala_loss(logits, baseline, actions, pg_advantages, vs):
 
 class _LstmUnroll(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, proj_mfma, x, notdone, h0, c0, *flat_weights):
+    def forward(ctx, proj_mfma, gate_mfma, x, notdone, h0, c0, *flat_weights):
         ext = _ext_for(x, "lstm_unroll_fwd")
         num_layers = len(flat_weights) // 4
         args = (
@@ -221,14 +221,19 @@ class _LstmUnroll(torch.autograd.Function):
             [w.contiguous() for w in flat_weights],
         )
         # TBAMD_LSTM_MFMA=1: the input projection on lstm_proj_mfma.hip.
-        results = (ext.lstm_unroll_fwd(*args, True) if proj_mfma
-                   else ext.lstm_unroll_fwd(*args))
+        # TBAMD_LSTM_GATE_MFMA=1: the recurrence on lstm_gate_mfma.hip.
+        if gate_mfma:
+            results = ext.lstm_unroll_fwd(*args, proj_mfma, True)
+        else:
+            results = (ext.lstm_unroll_fwd(*args, True) if proj_mfma
+                       else ext.lstm_unroll_fwd(*args))
         out, hT, cT = results[:3]
         # Per layer: input, gates, hm, cm, c (and the wt pack if proj_mfma).
         stash = results[3:]
         ctx.save_for_backward(notdone, h0, c0, *flat_weights, *stash)
         ctx.num_layers = num_layers
         ctx.proj_mfma = proj_mfma
+        ctx.gate_mfma = gate_mfma
         return out, hT, cT
 
     @staticmethod
@@ -249,11 +254,14 @@ class _LstmUnroll(torch.autograd.Function):
             d_hT.contiguous(),
             d_cT.contiguous(),
         )
-        grads = (ext.lstm_unroll_bwd(*args, True) if ctx.proj_mfma
-                 else ext.lstm_unroll_bwd(*args))
+        if ctx.gate_mfma:
+            grads = ext.lstm_unroll_bwd(*args, ctx.proj_mfma, True)
+        else:
+            grads = (ext.lstm_unroll_bwd(*args, True) if ctx.proj_mfma
+                     else ext.lstm_unroll_bwd(*args))
         d_x, d_h0, d_c0 = grads[:3]
         d_weights = grads[3:]
-        return (None, d_x, None, d_h0, d_c0, *d_weights)
+        return (None, None, d_x, None, d_h0, d_c0, *d_weights)
 
 
 def _lstm_proj_mfma(core, x, state):
@@ -272,6 +280,20 @@ def _lstm_proj_mfma(core, x, state):
         for layer in range(core.num_layers))
 
 
+def _lstm_gate_mfma(core, x, state):
+    """TBAMD_LSTM_GATE_MFMA=1 (--lstm_gate_mfma), fp32 on the GPU and (B, H)
+    accepted by the planner; unset, no lstm_gate_* symbol is touched."""
+    if os.environ.get("TBAMD_LSTM_GATE_MFMA") != "1":
+        return False
+    if x.dtype != torch.float32 or state[0].dtype != torch.float32:
+        return False
+    ext = _ext_for(x, "lstm_gate_supported")
+    return (
+        all(getattr(core, f"weight_hh_l{layer}").dtype == torch.float32
+            for layer in range(core.num_layers))
+        and ext.lstm_gate_supported(x.shape[1], core.hidden_size))
+
+
 def lstm_unroll(core, x, notdone, state):
     """Run `core` (an nn.LSTM) over x [T,B,I] with per-step done masking.
 
@@ -288,7 +310,8 @@ def lstm_unroll(core, x, notdone, state):
                 getattr(core, f"bias_ih_l{layer}"),
                 getattr(core, f"bias_hh_l{layer}"),
             ]
-        out, hT, cT = _LstmUnroll.apply(_lstm_proj_mfma(core, x, state), x,
+        out, hT, cT = _LstmUnroll.apply(_lstm_proj_mfma(core, x, state),
+                                        _lstm_gate_mfma(core, x, state), x,
                                         notdone, state[0], state[1], *flat)
         return out, (hT, cT)
 

@@ -31,6 +31,7 @@
 #include "conv_mfma.h"
 #include "heads_mfma.h"
 #include "linear_mfma.h"
+#include "lstm_gate_mfma.h"
 #include "lstm_proj_mfma.h"
 
 namespace tbamd {
@@ -659,11 +660,12 @@ void lstm4_bwd_launch(torch::Tensor gates, torch::Tensor cm,
 // Multi-layer forward. flat_weights: [w_ih, w_hh, b_ih, b_hh] per layer.
 // proj_mfma: the input projection on the bf16 MFMA kernels of
 // lstm_proj_mfma.hip; the stash then carries the [I, Np] weight pack as a
-// sixth entry per layer.
+// sixth entry per layer. gate_mfma: the recurrent kernels of
+// lstm_gate_mfma.hip instead of lstm4; the stash is the same.
 std::vector<torch::Tensor> lstm_unroll_fwd(
     torch::Tensor x, torch::Tensor notdone, torch::Tensor h0,
     torch::Tensor c0, std::vector<torch::Tensor> flat_weights,
-    bool proj_mfma = false) {
+    bool proj_mfma = false, bool gate_mfma = false) {
   TORCH_CHECK(x.is_cuda() && x.dim() == 3, "lstm: x must be [T,B,I] on GPU");
   const int T = x.size(0);
   const int B = x.size(1);
@@ -713,8 +715,13 @@ std::vector<torch::Tensor> lstm_unroll_fwd(
     auto c0_l = c0[l].contiguous();
 
     auto w_hh_bf = w_hh.to(torch::kBFloat16).contiguous();
-    tbamd::lstm4_fwd_launch(precomp, w_hh_bf, notdone_f, h0_l, c0_l, out,
-                            gates, hm, cm, c_out, hT[l], cT[l]);
+    if (gate_mfma) {
+      tbamd::lstm_gate_fwd_launch(precomp, w_hh_bf, notdone_f, h0_l, c0_l, out,
+                                  gates, hm, cm, c_out, hT[l], cT[l]);
+    } else {
+      tbamd::lstm4_fwd_launch(precomp, w_hh_bf, notdone_f, h0_l, c0_l, out,
+                              gates, hm, cm, c_out, hT[l], cT[l]);
+    }
 
     stash.push_back(layer_in);
     stash.push_back(gates);
@@ -734,7 +741,8 @@ std::vector<torch::Tensor> lstm_unroll_bwd(
     torch::Tensor notdone, torch::Tensor h0, torch::Tensor c0,
     std::vector<torch::Tensor> flat_weights,
     std::vector<torch::Tensor> stash, torch::Tensor d_out_top,
-    torch::Tensor d_hT, torch::Tensor d_cT, bool proj_mfma = false) {
+    torch::Tensor d_hT, torch::Tensor d_cT, bool proj_mfma = false,
+    bool gate_mfma = false) {
   const int L = flat_weights.size() / 4;
   const int per_layer = proj_mfma ? 6 : 5;
   TORCH_CHECK((int)stash.size() == per_layer * L, "lstm_unroll_bwd: stash of ",
@@ -759,16 +767,23 @@ std::vector<torch::Tensor> lstm_unroll_bwd(
     auto c_out = stash[per_layer * l + 4];
     auto w_ih = flat_weights[4 * l].contiguous();
     auto w_hh = flat_weights[4 * l + 1].contiguous();
-    auto w_hh_t_bf =
-        w_hh.t().contiguous().to(torch::kBFloat16).contiguous();  // [H,4H]
 
     auto dgates = torch::empty({T, B, 4 * H}, opts);
     auto dh = torch::empty({B, H}, opts);
     auto dc = torch::empty({B, H}, opts);
     auto d_hT_l = d_hT[l].contiguous();
     auto d_cT_l = d_cT[l].contiguous();
-    tbamd::lstm4_bwd_launch(gates, cm, c_out, w_hh_t_bf, notdone_f, d_out,
-                            d_hT_l, d_cT_l, dgates, dh, dc);
+    if (gate_mfma) {  // W_hh as [4H,H]: no transposed copy
+      tbamd::lstm_gate_bwd_launch(gates, cm, c_out,
+                                  w_hh.to(torch::kBFloat16).contiguous(),
+                                  notdone_f, d_out, d_hT_l, d_cT_l, dgates, dh,
+                                  dc);
+    } else {
+      auto w_hh_t_bf =
+          w_hh.t().contiguous().to(torch::kBFloat16).contiguous();  // [H,4H]
+      tbamd::lstm4_bwd_launch(gates, cm, c_out, w_hh_t_bf, notdone_f, d_out,
+                              d_hT_l, d_cT_l, dgates, dh, dc);
+    }
 
     // Weight/input grads: plain GEMMs (rocBLAS).
     auto dg2 = dgates.reshape({(int64_t)T * B, 4 * H});
@@ -833,6 +848,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lstm_proj_fwd", &tbamd::lstm_proj_fwd);
   m.def("lstm_proj_dgrad", &tbamd::lstm_proj_dgrad);
   m.def("lstm_proj_wgrad", &tbamd::lstm_proj_wgrad);
+  m.def("lstm_gate_supported", &tbamd::lstm_gate_supported);
+  m.def("lstm_gate_fwd", &tbamd::lstm_gate_fwd);
+  m.def("lstm_gate_bwd", &tbamd::lstm_gate_bwd);
   m.def("heads_supported", &tbamd::heads_supported);
   m.def("heads_fwd", &tbamd::heads_fwd);
   m.def("heads_dgrad", &tbamd::heads_dgrad);
@@ -863,9 +881,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("policy_sample", &policy_sample);
   m.def("lstm_unroll_fwd", &lstm_unroll_fwd, py::arg("x"), py::arg("notdone"),
         py::arg("h0"), py::arg("c0"), py::arg("flat_weights"),
-        py::arg("proj_mfma") = false);
+        py::arg("proj_mfma") = false, py::arg("gate_mfma") = false);
   m.def("lstm_unroll_bwd", &lstm_unroll_bwd, py::arg("notdone"), py::arg("h0"),
         py::arg("c0"), py::arg("flat_weights"), py::arg("stash"),
         py::arg("d_out_top"), py::arg("d_hT"), py::arg("d_cT"),
-        py::arg("proj_mfma") = false);
+        py::arg("proj_mfma") = false, py::arg("gate_mfma") = false);
 }
