@@ -50,6 +50,11 @@ def add_common_flags(parser: argparse.ArgumentParser):
                         help="Run the learner LSTM's recurrence (forward and "
                              "backward over time) on the persistent bf16 MFMA "
                              "gate kernels; same as TBAMD_LSTM_GATE_MFMA=1.")
+    parser.add_argument("--lstm_gate_wide", action="store_true",
+                        help="Run the learner LSTM's recurrence on the "
+                             "wide-batch persistent bf16 MFMA gate kernels "
+                             "when the learner batch is 65 to 256; same as "
+                             "TBAMD_LSTM_GATE_WIDE=1.")
     return parser
 
 
@@ -72,6 +77,13 @@ def apply_lstm_gate_mfma(flags):
     every forward. Without the flag the environment is left as it is."""
     if getattr(flags, "lstm_gate_mfma", False):
         os.environ["TBAMD_LSTM_GATE_MFMA"] = "1"
+
+
+def apply_lstm_gate_wide(flags):
+    """--lstm_gate_wide -> TBAMD_LSTM_GATE_WIDE=1, which lstm_unroll reads at
+    every forward. Without the flag the environment is left as it is."""
+    if getattr(flags, "lstm_gate_wide", False):
+        os.environ["TBAMD_LSTM_GATE_WIDE"] = "1"
 
 
 def apply_fc_mfma(flags):

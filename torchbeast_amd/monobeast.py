@@ -301,6 +301,7 @@ def train(flags):  # noqa: C901
     tbflags.apply_fc_mfma(flags)
     tbflags.apply_lstm_mfma(flags)
     tbflags.apply_lstm_gate_mfma(flags)
+    tbflags.apply_lstm_gate_wide(flags)
     tbflags.apply_heads_mfma(flags)
     if flags.xpid is None:
         flags.xpid = time.strftime("torchbeast-%Y%m%d-%H%M%S")

@@ -210,7 +210,8 @@ def fused_impala_loss(logits, baseline, actions, pg_advantages, vs):
 
 class _LstmUnroll(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, proj_mfma, gate_mfma, x, notdone, h0, c0, *flat_weights):
+    def forward(ctx, proj_mfma, gate_mfma, gate_wide, x, notdone, h0, c0,
+                *flat_weights):
         ext = _ext_for(x, "lstm_unroll_fwd")
         num_layers = len(flat_weights) // 4
         args = (
@@ -222,7 +223,10 @@ class _LstmUnroll(torch.autograd.Function):
         )
         # TBAMD_LSTM_MFMA=1: the input projection on lstm_proj_mfma.hip.
         # TBAMD_LSTM_GATE_MFMA=1: the recurrence on lstm_gate_mfma.hip.
-        if gate_mfma:
+        # TBAMD_LSTM_GATE_WIDE=1 and B > 64: on lstm_gate_wide.hip.
+        if gate_wide:
+            results = ext.lstm_unroll_fwd(*args, proj_mfma, False, True)
+        elif gate_mfma:
             results = ext.lstm_unroll_fwd(*args, proj_mfma, True)
         else:
             results = (ext.lstm_unroll_fwd(*args, True) if proj_mfma
@@ -234,6 +238,7 @@ class _LstmUnroll(torch.autograd.Function):
         ctx.num_layers = num_layers
         ctx.proj_mfma = proj_mfma
         ctx.gate_mfma = gate_mfma
+        ctx.gate_wide = gate_wide
         return out, hT, cT
 
     @staticmethod
@@ -254,14 +259,16 @@ class _LstmUnroll(torch.autograd.Function):
             d_hT.contiguous(),
             d_cT.contiguous(),
         )
-        if ctx.gate_mfma:
+        if ctx.gate_wide:
+            grads = ext.lstm_unroll_bwd(*args, ctx.proj_mfma, False, True)
+        elif ctx.gate_mfma:
             grads = ext.lstm_unroll_bwd(*args, ctx.proj_mfma, True)
         else:
             grads = (ext.lstm_unroll_bwd(*args, True) if ctx.proj_mfma
                      else ext.lstm_unroll_bwd(*args))
         d_x, d_h0, d_c0 = grads[:3]
         d_weights = grads[3:]
-        return (None, None, d_x, None, d_h0, d_c0, *d_weights)
+        return (None, None, None, d_x, None, d_h0, d_c0, *d_weights)
 
 
 def _lstm_proj_mfma(core, x, state):
@@ -294,6 +301,21 @@ def _lstm_gate_mfma(core, x, state):
         and ext.lstm_gate_supported(x.shape[1], core.hidden_size))
 
 
+def _lstm_gate_wide(core, x, state):
+    """TBAMD_LSTM_GATE_WIDE=1 (--lstm_gate_wide), B > 64, fp32 on the GPU and
+    (B, H) accepted by the planner; unset, no lstm_gate_wide_* symbol is
+    touched. Batches up to 64 are never sent to the wide kernels."""
+    if os.environ.get("TBAMD_LSTM_GATE_WIDE") != "1" or x.shape[1] <= 64:
+        return False
+    if x.dtype != torch.float32 or state[0].dtype != torch.float32:
+        return False
+    ext = _ext_for(x, "lstm_gate_wide_supported")
+    return (
+        all(getattr(core, f"weight_hh_l{layer}").dtype == torch.float32
+            for layer in range(core.num_layers))
+        and ext.lstm_gate_wide_supported(x.shape[1], core.hidden_size))
+
+
 def lstm_unroll(core, x, notdone, state):
     """Run `core` (an nn.LSTM) over x [T,B,I] with per-step done masking.
 
@@ -311,7 +333,8 @@ def lstm_unroll(core, x, notdone, state):
                 getattr(core, f"bias_hh_l{layer}"),
             ]
         out, hT, cT = _LstmUnroll.apply(_lstm_proj_mfma(core, x, state),
-                                        _lstm_gate_mfma(core, x, state), x,
+                                        _lstm_gate_mfma(core, x, state),
+                                        _lstm_gate_wide(core, x, state), x,
                                         notdone, state[0], state[1], *flat)
         return out, (hT, cT)
 

@@ -32,6 +32,7 @@
 #include "heads_mfma.h"
 #include "linear_mfma.h"
 #include "lstm_gate_mfma.h"
+#include "lstm_gate_wide.h"
 #include "lstm_proj_mfma.h"
 
 namespace tbamd {
@@ -661,11 +662,12 @@ void lstm4_bwd_launch(torch::Tensor gates, torch::Tensor cm,
 // proj_mfma: the input projection on the bf16 MFMA kernels of
 // lstm_proj_mfma.hip; the stash then carries the [I, Np] weight pack as a
 // sixth entry per layer. gate_mfma: the recurrent kernels of
-// lstm_gate_mfma.hip instead of lstm4; the stash is the same.
+// lstm_gate_mfma.hip instead of lstm4; the stash is the same. gate_wide: the
+// wide-batch recurrent kernels of lstm_gate_wide.hip, likewise.
 std::vector<torch::Tensor> lstm_unroll_fwd(
     torch::Tensor x, torch::Tensor notdone, torch::Tensor h0,
     torch::Tensor c0, std::vector<torch::Tensor> flat_weights,
-    bool proj_mfma = false, bool gate_mfma = false) {
+    bool proj_mfma = false, bool gate_mfma = false, bool gate_wide = false) {
   TORCH_CHECK(x.is_cuda() && x.dim() == 3, "lstm: x must be [T,B,I] on GPU");
   const int T = x.size(0);
   const int B = x.size(1);
@@ -715,7 +717,11 @@ std::vector<torch::Tensor> lstm_unroll_fwd(
     auto c0_l = c0[l].contiguous();
 
     auto w_hh_bf = w_hh.to(torch::kBFloat16).contiguous();
-    if (gate_mfma) {
+    if (gate_wide) {
+      tbamd::lstm_gate_wide_fwd_launch(precomp, w_hh_bf, notdone_f, h0_l, c0_l,
+                                       out, gates, hm, cm, c_out, hT[l],
+                                       cT[l]);
+    } else if (gate_mfma) {
       tbamd::lstm_gate_fwd_launch(precomp, w_hh_bf, notdone_f, h0_l, c0_l, out,
                                   gates, hm, cm, c_out, hT[l], cT[l]);
     } else {
@@ -742,7 +748,7 @@ std::vector<torch::Tensor> lstm_unroll_bwd(
     std::vector<torch::Tensor> flat_weights,
     std::vector<torch::Tensor> stash, torch::Tensor d_out_top,
     torch::Tensor d_hT, torch::Tensor d_cT, bool proj_mfma = false,
-    bool gate_mfma = false) {
+    bool gate_mfma = false, bool gate_wide = false) {
   const int L = flat_weights.size() / 4;
   const int per_layer = proj_mfma ? 6 : 5;
   TORCH_CHECK((int)stash.size() == per_layer * L, "lstm_unroll_bwd: stash of ",
@@ -773,7 +779,12 @@ std::vector<torch::Tensor> lstm_unroll_bwd(
     auto dc = torch::empty({B, H}, opts);
     auto d_hT_l = d_hT[l].contiguous();
     auto d_cT_l = d_cT[l].contiguous();
-    if (gate_mfma) {  // W_hh as [4H,H]: no transposed copy
+    if (gate_wide) {  // W_hh as [4H,H]: no transposed copy
+      tbamd::lstm_gate_wide_bwd_launch(gates, cm, c_out,
+                                       w_hh.to(torch::kBFloat16).contiguous(),
+                                       notdone_f, d_out, d_hT_l, d_cT_l,
+                                       dgates, dh, dc);
+    } else if (gate_mfma) {  // likewise
       tbamd::lstm_gate_bwd_launch(gates, cm, c_out,
                                   w_hh.to(torch::kBFloat16).contiguous(),
                                   notdone_f, d_out, d_hT_l, d_cT_l, dgates, dh,
@@ -851,6 +862,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("lstm_gate_supported", &tbamd::lstm_gate_supported);
   m.def("lstm_gate_fwd", &tbamd::lstm_gate_fwd);
   m.def("lstm_gate_bwd", &tbamd::lstm_gate_bwd);
+  m.def("lstm_gate_wide_supported", &tbamd::lstm_gate_wide_supported);
+  m.def("lstm_gate_wide_fwd", &tbamd::lstm_gate_wide_fwd);
+  m.def("lstm_gate_wide_bwd", &tbamd::lstm_gate_wide_bwd);
   m.def("heads_supported", &tbamd::heads_supported);
   m.def("heads_fwd", &tbamd::heads_fwd);
   m.def("heads_dgrad", &tbamd::heads_dgrad);
@@ -881,9 +895,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("policy_sample", &policy_sample);
   m.def("lstm_unroll_fwd", &lstm_unroll_fwd, py::arg("x"), py::arg("notdone"),
         py::arg("h0"), py::arg("c0"), py::arg("flat_weights"),
-        py::arg("proj_mfma") = false, py::arg("gate_mfma") = false);
+        py::arg("proj_mfma") = false, py::arg("gate_mfma") = false,
+        py::arg("gate_wide") = false);
   m.def("lstm_unroll_bwd", &lstm_unroll_bwd, py::arg("notdone"), py::arg("h0"),
         py::arg("c0"), py::arg("flat_weights"), py::arg("stash"),
         py::arg("d_out_top"), py::arg("d_hT"), py::arg("d_cT"),
-        py::arg("proj_mfma") = false, py::arg("gate_mfma") = false);
+        py::arg("proj_mfma") = false, py::arg("gate_mfma") = false,
+        py::arg("gate_wide") = false);
 }

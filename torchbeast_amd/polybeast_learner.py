@@ -396,6 +396,7 @@ def train(flags):  # noqa: C901
     tbflags.apply_fc_mfma(flags)
     tbflags.apply_lstm_mfma(flags)
     tbflags.apply_lstm_gate_mfma(flags)
+    tbflags.apply_lstm_gate_wide(flags)
     tbflags.apply_heads_mfma(flags)
     rank, world_size, local_rank = tbddp.maybe_init_distributed()
     is_leader = rank == 0
