@@ -55,6 +55,10 @@ def add_common_flags(parser: argparse.ArgumentParser):
                              "wide-batch persistent bf16 MFMA gate kernels "
                              "when the learner batch is 65 to 256; same as "
                              "TBAMD_LSTM_GATE_WIDE=1.")
+    parser.add_argument("--fused_tail", action="store_true",
+                        help="Run the learner's V-trace, losses and their "
+                             "gradients as one kernel (at most 64 actions); "
+                             "same as TBAMD_FUSED_TAIL=1.")
     return parser
 
 
@@ -84,6 +88,13 @@ def apply_lstm_gate_wide(flags):
     every forward. Without the flag the environment is left as it is."""
     if getattr(flags, "lstm_gate_wide", False):
         os.environ["TBAMD_LSTM_GATE_WIDE"] = "1"
+
+
+def apply_fused_tail(flags):
+    """--fused_tail -> TBAMD_FUSED_TAIL=1, which learner_tail reads at every
+    step. Without the flag the environment is left as it is."""
+    if getattr(flags, "fused_tail", False):
+        os.environ["TBAMD_FUSED_TAIL"] = "1"
 
 
 def apply_fc_mfma(flags):

@@ -29,9 +29,8 @@ from torch import multiprocessing as mp
 from torch import nn
 
 from torchbeast_amd import flags as tbflags
-from torchbeast_amd.core import environment, file_writer, prof, vtrace
+from torchbeast_amd.core import environment, file_writer, prof, tail
 from torchbeast_amd.models.atari_net import AtariNet
-from torchbeast_amd.ops import functional as tbops
 
 # The reference exports its model under both names; keep that surface.
 Net = AtariNet
@@ -239,42 +238,19 @@ def learn(
     with lock:
         learner_outputs, _ = model(batch, initial_agent_state)
 
-        # The value estimate at the last row bootstraps the returns.
-        bootstrap_value = learner_outputs["baseline"][-1]
-
-        # Re-align so that row t pairs action[t] with its consequence.
-        batch = {name: t[1:] for name, t in batch.items()}
-        learner_outputs = {name: t[:-1] for name, t in learner_outputs.items()}
-
-        if flags.reward_clipping == "abs_one":
-            rewards = torch.clamp(batch["reward"], -1, 1)
-        else:
-            rewards = batch["reward"]
-        discounts = (~batch["done"]).float() * flags.discounting
-
-        targets = vtrace.from_logits(
-            behavior_policy_logits=batch["policy_logits"],
-            target_policy_logits=learner_outputs["policy_logits"],
-            actions=batch["action"],
-            discounts=discounts,
-            rewards=rewards,
-            values=learner_outputs["baseline"],
-            bootstrap_value=bootstrap_value,
-            lambda_=flags.vtrace_lambda,
-        )
-
-        pg_loss, baseline_loss, entropy_loss = tbops.fused_impala_loss(
+        # V-trace, the three losses and their total (core/tail.py).
+        total_loss, pg_loss, baseline_loss, entropy_loss = tail.learner_tail(
+            flags,
+            batch["reward"],
+            batch["done"],
+            batch["policy_logits"],
+            batch["action"],
             learner_outputs["policy_logits"],
             learner_outputs["baseline"],
-            batch["action"],
-            targets.pg_advantages,
-            targets.vs,
         )
-        total_loss = (
-            pg_loss
-            + flags.baseline_cost * baseline_loss
-            + flags.entropy_cost * entropy_loss
-        )
+
+        # Row t + 1 of the batch is the consequence of action t.
+        batch = {name: t[1:] for name, t in batch.items()}
 
         finished = batch["episode_return"][batch["done"]]
         stats = {
@@ -303,6 +279,7 @@ def train(flags):  # noqa: C901
     tbflags.apply_lstm_gate_mfma(flags)
     tbflags.apply_lstm_gate_wide(flags)
     tbflags.apply_heads_mfma(flags)
+    tbflags.apply_fused_tail(flags)
     if flags.xpid is None:
         flags.xpid = time.strftime("torchbeast-%Y%m%d-%H%M%S")
     plogger = file_writer.FileWriter(

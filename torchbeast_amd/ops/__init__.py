@@ -8,6 +8,8 @@ wraps them in `torch.autograd.Function`s and exposes:
 - `vtrace_from_logits(...)`         — fused V-trace (log-probs + clip + scan)
 - `vtrace_from_importance_weights(...)` — the same scan from given log_rhos
 - `fused_impala_loss(...)`          — all three losses + grads in one kernel
+- `impala_tail(...)`                — V-trace, losses, total and its grads for
+                                      an unshifted [T+1, B] batch, one kernel
 - `lstm_unroll(...)`                — done-masked multi-layer LSTM over T
 - `rmsprop_step(...)`               — fused global-norm clip + RMSProp
 - `policy_sample(...)`              — softmax + multinomial / argmax
@@ -79,6 +81,7 @@ def require_ext():
 # Fused-op wrappers are defined in submodules to keep this init cheap.
 from torchbeast_amd.ops.functional import (  # noqa: E402,F401
     fused_impala_loss,
+    impala_tail,
     lstm_unroll,
     policy_sample,
     rmsprop_step,

@@ -204,6 +204,135 @@ def fused_impala_loss(logits, baseline, actions, pg_advantages, vs):
 
 
 # ---------------------------------------------------------------------------
+# The learner tail in one launch: reward clip, discounts, V-trace, the three
+# losses, their weighted total and its gradients (ops/hip/impala_tail.hip).
+# ---------------------------------------------------------------------------
+
+
+class _ImpalaTail(torch.autograd.Function):
+    """Forward computes the four scalars AND d total / d (target_logits,
+    baseline), already laid out for T + 1 rows; backward scales the two saved
+    gradients by the incoming scalar. Only total is differentiable."""
+
+    @staticmethod
+    def forward(ctx, target_logits, baseline, behavior_logits, actions,
+                rewards, done, discounting, clip_reward, clip_rho, clip_pg,
+                lambda_, baseline_cost, entropy_cost):
+        ext = _ext_for(target_logits, "impala_tail_fwd")
+        losses, d_logits, d_baseline, _, _ = ext.impala_tail_fwd(
+            behavior_logits.detach().contiguous(),
+            target_logits.detach().contiguous(),
+            actions.contiguous(),
+            rewards.detach().contiguous(),
+            done.contiguous(),
+            baseline.detach().contiguous(),
+            discounting, clip_reward, clip_rho, clip_pg, lambda_,
+            baseline_cost, entropy_cost,
+        )
+        ctx.save_for_backward(d_logits, d_baseline)
+        total, pg_loss, baseline_loss, entropy_loss = (losses[i] for i in range(4))
+        ctx.mark_non_differentiable(pg_loss, baseline_loss, entropy_loss)
+        # No zero tensors for the three gradients that cannot arrive.
+        ctx.set_materialize_grads(False)
+        return total, pg_loss, baseline_loss, entropy_loss
+
+    @staticmethod
+    def backward(ctx, g_total, _g_pg, _g_bl, _g_ent):
+        if g_total is None:
+            return (None,) * 13
+        d_logits, d_baseline = ctx.saved_tensors
+        return (g_total * d_logits, g_total * d_baseline) + (None,) * 11
+
+
+def impala_tail_eager(
+    behavior_policy_logits,
+    target_policy_logits,
+    actions,
+    rewards,
+    done,
+    baseline,
+    discounting,
+    clip_reward=True,
+    clip_rho_threshold=1.0,
+    clip_pg_rho_threshold=1.0,
+    lambda_=1.0,
+    baseline_cost=0.5,
+    entropy_cost=0.0006,
+):
+    """The tail as the trainers used to spell it: shift, clip, discounts,
+    vtrace.from_logits, fused_impala_loss, weighted total. The CPU path of
+    impala_tail and, in float64, its numerics oracle."""
+    from torchbeast_amd.core import vtrace as pyvtrace
+
+    bootstrap_value = baseline[-1]
+    behavior_policy_logits, actions = behavior_policy_logits[1:], actions[1:]
+    rewards, done = rewards[1:], done[1:]
+    target_policy_logits, baseline = target_policy_logits[:-1], baseline[:-1]
+    if clip_reward:
+        rewards = torch.clamp(rewards, -1, 1)
+    discounts = (~done).to(rewards.dtype) * discounting
+    vtrace_returns = pyvtrace.from_logits(
+        behavior_policy_logits=behavior_policy_logits,
+        target_policy_logits=target_policy_logits,
+        actions=actions,
+        discounts=discounts,
+        rewards=rewards,
+        values=baseline,
+        bootstrap_value=bootstrap_value,
+        clip_rho_threshold=clip_rho_threshold,
+        clip_pg_rho_threshold=clip_pg_rho_threshold,
+        lambda_=lambda_,
+    )
+    pg_loss, baseline_loss, entropy_loss = fused_impala_loss(
+        target_policy_logits,
+        baseline,
+        actions,
+        vtrace_returns.pg_advantages,
+        vtrace_returns.vs,
+    )
+    total_loss = pg_loss + baseline_cost * baseline_loss + entropy_cost * entropy_loss
+    return total_loss, pg_loss, baseline_loss, entropy_loss
+
+
+def impala_tail(
+    behavior_policy_logits,
+    target_policy_logits,
+    actions,
+    rewards,
+    done,
+    baseline,
+    discounting,
+    clip_reward=True,
+    clip_rho_threshold=1.0,
+    clip_pg_rho_threshold=1.0,
+    lambda_=1.0,
+    baseline_cost=0.5,
+    entropy_cost=0.0006,
+):
+    """Return (total, pg, baseline, entropy) scalars for a [T+1, B] batch.
+
+    All six tensors are unshifted, as the queue and the model produce them:
+    logits [T+1, B, A] float32 (A <= 64), actions int32 or int64, rewards and
+    baseline float32, done bool. Row t of target_policy_logits and baseline
+    meets row t + 1 of the others; baseline[-1] bootstraps. Only total is
+    differentiable, with respect to target_policy_logits and baseline.
+    """
+    from torchbeast_amd.core import vtrace as pyvtrace
+
+    lambda_ = pyvtrace.check_lambda(lambda_)
+    if _ext_for(target_policy_logits, "impala_tail_fwd") is None:
+        return impala_tail_eager(
+            behavior_policy_logits, target_policy_logits, actions, rewards,
+            done, baseline, discounting, clip_reward, clip_rho_threshold,
+            clip_pg_rho_threshold, lambda_, baseline_cost, entropy_cost)
+    return _ImpalaTail.apply(
+        target_policy_logits, baseline, behavior_policy_logits, actions,
+        rewards, done, float(discounting), bool(clip_reward),
+        _clip_or_inf(clip_rho_threshold), _clip_or_inf(clip_pg_rho_threshold),
+        lambda_, float(baseline_cost), float(entropy_cost))
+
+
+# ---------------------------------------------------------------------------
 # Done-masked LSTM unroll over T (multi-layer).
 # ---------------------------------------------------------------------------
 

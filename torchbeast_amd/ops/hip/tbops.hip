@@ -30,10 +30,12 @@
 #include "atari_trunk.h"
 #include "conv_mfma.h"
 #include "heads_mfma.h"
+#include "impala_tail.h"
 #include "linear_mfma.h"
 #include "lstm_gate_mfma.h"
 #include "lstm_gate_wide.h"
 #include "lstm_proj_mfma.h"
+#include "vtrace_math.h"
 
 namespace tbamd {
 std::vector<double> barrier_probe(int64_t variant, int64_t wgs, int64_t iters);
@@ -50,35 +52,8 @@ static inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b)
 // V-trace: log-probs + rho/c clip + reverse scan + pg advantages, one launch.
 // ---------------------------------------------------------------------------
 
-// The per-element arithmetic shared by vtrace_kernel (from logits) and
-// vtrace_iw_kernel (from log_rhos): both call these, so the two entry points
-// cannot drift. A clip threshold of +inf means "do not clip": fminf(rho, inf)
-// is rho exactly. c is clipped at 1 regardless, then scaled by lambda
-// (arXiv:1802.01561 Remark 2); lambda = 1 multiplies exactly.
-__device__ __forceinline__ void vtrace_clip(float log_rho, float clip_rho,
-                                            float lambda, float* crho,
-                                            float* c) {
-  const float rho = __expf(log_rho);
-  *crho = fminf(rho, clip_rho);
-  *c = lambda * fminf(rho, 1.f);
-}
-
-__device__ __forceinline__ float vtrace_delta(float crho, float r, float disc,
-                                              float v_next, float v) {
-  return crho * (r + disc * v_next - v);
-}
-
-__device__ __forceinline__ float vtrace_scan_step(float delta, float disc,
-                                                  float c, float acc) {
-  return delta + disc * c * acc;
-}
-
-__device__ __forceinline__ float vtrace_advantage(float log_rho, float clip_pg,
-                                                  float r, float disc,
-                                                  float vs_next, float v) {
-  const float rho = __expf(log_rho);
-  return fminf(rho, clip_pg) * (r + disc * vs_next - v);
-}
+// The per-element arithmetic (vtrace_clip, vtrace_delta, vtrace_scan_step,
+// vtrace_advantage) is in vtrace_math.h, shared with impala_tail.hip.
 
 // Phases 2 and 3 of both kernels, entered after phase 1 has filled s_cs and
 // s_delta: the reverse recurrence on one thread, then vs and pg_adv
@@ -871,6 +846,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("heads_wgrad", &tbamd::heads_wgrad, py::arg("x"), py::arg("reward"),
         py::arg("last_action"), py::arg("dlogits"), py::arg("dbaseline"),
         py::arg("num_actions") = -1);
+  m.def("impala_tail_fwd", &tbamd::impala_tail_fwd,
+        py::arg("behavior_logits"), py::arg("target_logits"),
+        py::arg("actions"), py::arg("rewards"), py::arg("done"),
+        py::arg("baseline"), py::arg("discounting"), py::arg("clip_reward"),
+        py::arg("clip_rho"), py::arg("clip_pg"), py::arg("lambda_"),
+        py::arg("baseline_cost"), py::arg("entropy_cost"));
   m.def("barrier_probe", &tbamd::barrier_probe);
   m.def("launch_probe", &tbamd::launch_probe);
   m.def("mfma_gemm", &tbamd::mfma_gemm);

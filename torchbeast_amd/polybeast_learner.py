@@ -29,10 +29,9 @@ import torch
 
 from torchbeast_amd import flags as tbflags
 from torchbeast_amd import runtime
-from torchbeast_amd.core import file_writer, vtrace
+from torchbeast_amd.core import file_writer, tail
 from torchbeast_amd.models.atari_net import AtariNet
 from torchbeast_amd.models.resnet import ResNet
-from torchbeast_amd.ops import functional as tbops
 from torchbeast_amd.parallel import ddp as tbddp
 from torchbeast_amd.parallel import flat as tbflat
 
@@ -240,42 +239,15 @@ def learn(
         )
         learner_outputs = AgentOutput._make(_as_agent_output(learner_outputs))
 
-        bootstrap_value = learner_outputs.baseline[-1]
-
-        # Shift: env_outputs[t+1] is the consequence of actions[t].
-        env_outputs = EnvOutput._make(t[1:] for t in env_outputs)
-        actor_outputs = AgentOutput._make(t[1:] for t in actor_outputs)
-        learner_outputs = AgentOutput._make(t[:-1] for t in learner_outputs)
-
-        if flags.reward_clipping == "abs_one":
-            clipped_rewards = torch.clamp(env_outputs.rewards, -1, 1)
-        else:
-            clipped_rewards = env_outputs.rewards
-
-        discounts = (~env_outputs.done).float() * flags.discounting
-
-        vtrace_returns = vtrace.from_logits(
-            behavior_policy_logits=actor_outputs.policy_logits,
-            target_policy_logits=learner_outputs.policy_logits,
-            actions=actor_outputs.action,
-            discounts=discounts,
-            rewards=clipped_rewards,
-            values=learner_outputs.baseline,
-            bootstrap_value=bootstrap_value,
-            lambda_=flags.vtrace_lambda,
-        )
-
-        pg_loss, baseline_loss, entropy_loss = tbops.fused_impala_loss(
+        # V-trace, the three losses and their total (core/tail.py).
+        total_loss, pg_loss, baseline_loss, entropy_loss = tail.learner_tail(
+            flags,
+            env_outputs.rewards,
+            env_outputs.done,
+            actor_outputs.policy_logits,
+            actor_outputs.action,
             learner_outputs.policy_logits,
             learner_outputs.baseline,
-            actor_outputs.action,
-            vtrace_returns.pg_advantages,
-            vtrace_returns.vs,
-        )
-        total_loss = (
-            pg_loss
-            + flags.baseline_cost * baseline_loss
-            + flags.entropy_cost * entropy_loss
         )
 
         optimizer.zero_grad()
@@ -398,6 +370,7 @@ def train(flags):  # noqa: C901
     tbflags.apply_lstm_gate_mfma(flags)
     tbflags.apply_lstm_gate_wide(flags)
     tbflags.apply_heads_mfma(flags)
+    tbflags.apply_fused_tail(flags)
     rank, world_size, local_rank = tbddp.maybe_init_distributed()
     is_leader = rank == 0
     torch.manual_seed(4242 + rank * 977)
