@@ -33,6 +33,11 @@ def add_common_flags(parser: argparse.ArgumentParser):
                              "MFMA conv kernels at frame sizes other than "
                              "84x84 (up to 256x256), in the learner and the "
                              "C++ runner; same as TBAMD_RESNET_ANY=1.")
+    parser.add_argument("--resnet_glue", action="store_true",
+                        help="Run the learner's deep ResNet max-pools, ReLUs, "
+                             "residual adds and final flatten on the HIP glue "
+                             "kernels instead of ATen; same as "
+                             "TBAMD_RESNET_GLUE=1.")
     parser.add_argument("--fc_mfma", action="store_true",
                         help="Run the fully connected layer behind the conv "
                              "trunk on the bf16 MFMA linear kernels, in the "
@@ -111,6 +116,13 @@ def apply_resnet_any_geometry(flags):
     exists. Without the flag the environment is left as it is."""
     if getattr(flags, "resnet_any_geometry", False):
         os.environ["TBAMD_RESNET_ANY"] = "1"
+
+
+def apply_resnet_glue(flags):
+    """--resnet_glue -> TBAMD_RESNET_GLUE=1, which the model reads at every
+    forward. Without the flag the environment is left as it is."""
+    if getattr(flags, "resnet_glue", False):
+        os.environ["TBAMD_RESNET_GLUE"] = "1"
 
 
 def add_loss_flags(parser: argparse.ArgumentParser):

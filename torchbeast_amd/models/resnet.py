@@ -10,6 +10,9 @@ NCHW order in both paths so checkpoints transfer between CPU and GPU.
 With TBAMD_RESNET_ANY=1 (--resnet_any_geometry) every other frame size up
 to 256x256 takes the same path on the run-time-geometry kernels
 (conv_any_kernel / wgrad_any_kernel); unset, those frames stay on ATen.
+With TBAMD_RESNET_GLUE=1 (--resnet_glue) the max-pools, ReLUs, residual
+adds and the final ReLU + flatten run on the resnet_glue.hip kernels
+instead of ATen, with bit-identical features.
 
 Three feature sections with channel widths [16, 32, 32]; each section is a
 3x3 s1 p1 conv, a 3x3 s2 p1 max-pool, and two residual blocks of
@@ -82,11 +85,45 @@ class ResNet(nn.Module):
         self.policy = nn.Linear(core_size, num_actions)
         self.baseline = nn.Linear(core_size, 1)
 
-    def _features_mfma(self, x):
+    def _features_glue(self, x, flat):
+        """_features_mfma with everything between the convs on the glue
+        kernels (ops/hip/resnet_glue.hip) instead of ATen. flat: return
+        relu(features) as fp32 [N, C*H*W] from the flatten kernel."""
+        from torchbeast_amd.ops import functional as tbf
+
+        def section(sec, x):
+            # y is the skip of the first block, r = relu(y) its conv input.
+            y, r = tbf.glue_pool(x)
+            out = tbf.resnet_conv3x3(sec.res0.conv0, r)
+            out = tbf.resnet_conv3x3(sec.res0.conv1, tbf.glue_relu(out))
+            z, r = tbf.glue_add_relu(out, y)
+            out = tbf.resnet_conv3x3(sec.res1.conv0, r)
+            out = tbf.resnet_conv3x3(sec.res1.conv1, tbf.glue_relu(out))
+            return tbf.glue_add(out, z)
+
+        s1, s2, s3 = self.feat_extract
+        # The first conv's output is NHWC-dense already; the layout is made
+        # explicit here because the pool kernel takes nothing else.
+        x = tbf.resnet_first_conv(s1.conv, x)
+        x = x.contiguous(memory_format=torch.channels_last)
+        if tbf.resnet_glue(x) is None:
+            raise RuntimeError(
+                "TBAMD_RESNET_GLUE=1, but the glue kernels do not take the "
+                f"first conv's output ({x.dtype}, {tuple(x.shape)})")
+        x = section(s1, x)
+        x = section(s2, tbf.resnet_conv3x3(s2.conv, x))
+        x = section(s3, tbf.resnet_conv3x3(s3.conv, x))
+        return tbf.glue_flatten_relu(x) if flat else x.float()
+
+    def _features_mfma(self, x, flat=False):
         """Trunk on the MFMA conv kernels, bf16 channels_last: the template
         kernels at the 84x84 geometries, the run-time-geometry ones at any
         other (H, W)."""
         from torchbeast_amd.ops import functional as tbf
+
+        # Opt-in: max-pool, ReLU, skip add and flatten on HIP kernels too.
+        if os.environ.get("TBAMD_RESNET_GLUE") == "1":
+            return self._features_glue(x, flat)
 
         cl = torch.channels_last
 
@@ -125,19 +162,22 @@ class ResNet(nn.Module):
             ci = co
         return all(tbf.resnet_conv_any_supported(*c) for c in convs)
 
-    def _features(self, x):
+    def _features(self, x, flat=False):
+        """Trunk features [N, C, H, W] before the final ReLU. With flat=True
+        the glue path (TBAMD_RESNET_GLUE=1) may instead return them ReLU'd
+        and flattened, [N, C*H*W]; the caller tells by dim()."""
         if (x.is_cuda and x.shape[1] <= 8
                 and os.environ.get("TBAMD_RESNET") != "aten"):
             from torchbeast_amd.ops import functional as tbf
 
             if x.shape[2:] == (84, 84):
                 if tbf.resnet_conv3x3_supported(16, 42, 16):
-                    return self._features_mfma(x)
+                    return self._features_mfma(x, flat)
             elif (os.environ.get("TBAMD_RESNET_ANY") == "1"
                     and self._any_geometry_supported(*x.shape[2:])):
                 # Opt-in: any other frame size on the run-time-geometry
                 # MFMA kernels instead of fp32 library convs.
-                return self._features_mfma(x)
+                return self._features_mfma(x, flat)
         return self.feat_extract(x)
 
     def initial_state(self, batch_size=1):
@@ -152,10 +192,11 @@ class ResNet(nn.Module):
         frame, reward, done = inputs["frame"], inputs["reward"], inputs["done"]
         T, B = frame.shape[:2]
         x = torch.flatten(frame, 0, 1).float() / 255.0
-        x = self._features(x)
-        # reshape (not view): the MFMA path returns channels_last; logical
-        # NCHW flatten order is preserved either way.
-        x = F.relu(x).reshape(T * B, -1)
+        x = self._features(x, flat=True)
+        if x.dim() == 4:  # not ReLU'd and flattened by the glue kernels
+            # reshape (not view): the MFMA path returns channels_last;
+            # logical NCHW flatten order is preserved either way.
+            x = F.relu(x).reshape(T * B, -1)
         from torchbeast_amd.ops import functional as tbf
 
         # TBAMD_FC_MFMA=1: the fc on the bf16 MFMA linear kernels.

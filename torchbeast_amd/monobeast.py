@@ -274,6 +274,7 @@ def learn(
 
 def train(flags):  # noqa: C901
     tbflags.apply_resnet_any_geometry(flags)
+    tbflags.apply_resnet_glue(flags)
     tbflags.apply_fc_mfma(flags)
     tbflags.apply_lstm_mfma(flags)
     tbflags.apply_lstm_gate_mfma(flags)

@@ -811,6 +811,121 @@ def resnet_conv3x3_supported(ci, hw, co):
 
 
 # ---------------------------------------------------------------------------
+# Deep-ResNet glue between the convs (resnet_glue.hip): max-pool + ReLU,
+# ReLU / skip add, and the ReLU + fp32 NCHW flatten at the trunk's exit, on
+# bf16 channels_last activations; opt-in with TBAMD_RESNET_GLUE=1
+# (--resnet_glue).
+# ---------------------------------------------------------------------------
+
+
+def _glue_cl(t):
+    """A gradient as the glue kernels take it: bf16, channels_last."""
+    if t is None:
+        return None
+    return t.to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
+
+
+class _GluePool(torch.autograd.Function):
+    """(y, r) = (maxpool3x3 s2 p1 (x), relu(y)). Backward gathers dx from
+    g_y + g_r [y > 0] in one pass; the mask is read from r, which the next
+    conv keeps alive anyway."""
+
+    @staticmethod
+    def forward(ctx, x):
+        ext = _ext_for(x, "resnet_glue_pool_fwd")
+        y, r, idx = ext.resnet_glue_pool_fwd(x)
+        ctx.save_for_backward(r, idx)
+        ctx.hw = (x.shape[2], x.shape[3])
+        ctx.set_materialize_grads(False)
+        return y, r
+
+    @staticmethod
+    def backward(ctx, g_y, g_r):
+        if g_y is None and g_r is None:
+            return None
+        r, idx = ctx.saved_tensors
+        ext = ops_mod.require_ext()
+        return ext.resnet_glue_pool_bwd(_glue_cl(g_y), _glue_cl(g_r), r, idx,
+                                        *ctx.hw)
+
+
+class _GlueEw(torch.autograd.Function):
+    """(z, r) = (a + s, relu(z)); without s, z is a and only r is made;
+    without want_r only z. Both inputs get the one tensor
+    g_z + g_r [z > 0], which nothing downstream may modify in place."""
+
+    @staticmethod
+    def forward(ctx, a, s, want_r):
+        ext = _ext_for(a, "resnet_glue_ew_fwd")
+        z, r = ext.resnet_glue_ew_fwd(a, s, want_r)
+        ctx.save_for_backward(r)  # r > 0 exactly where z > 0
+        ctx.has_s = s is not None
+        ctx.set_materialize_grads(False)
+        return z, r
+
+    @staticmethod
+    def backward(ctx, g_z, g_r):
+        if g_z is None and g_r is None:
+            return None, None, None
+        (r,) = ctx.saved_tensors
+        ext = ops_mod.require_ext()
+        g = ext.resnet_glue_ew_bwd(_glue_cl(g_z), _glue_cl(g_r), r)
+        return g, (g if ctx.has_s else None), None
+
+
+class _GlueFlat(torch.autograd.Function):
+    """relu(x) as fp32 [N, C*H*W] in NCHW order, and its backward."""
+
+    @staticmethod
+    def forward(ctx, x):
+        ext = _ext_for(x, "resnet_glue_flat_fwd")
+        ctx.save_for_backward(x)
+        return ext.resnet_glue_flat_fwd(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        (x,) = ctx.saved_tensors
+        ext = ops_mod.require_ext()
+        return ext.resnet_glue_flat_bwd(g.float().contiguous(), x)
+
+
+def resnet_glue(x):
+    """The extension if the glue kernels apply to activation x, else None:
+    switch unset, not a CUDA bf16 channels_last [N, C, H, W] tensor, or C
+    not 16 or 32."""
+    if os.environ.get("TBAMD_RESNET_GLUE") != "1" or not x.is_cuda:
+        return None
+    if (x.dim() != 4 or x.dtype != torch.bfloat16 or x.shape[1] not in (16, 32)
+            or not x.is_contiguous(memory_format=torch.channels_last)
+            or x.data_ptr() % 16):
+        return None
+    return _ext_for(x, "resnet_glue_pool_fwd")
+
+
+def glue_pool(x):
+    """(maxpool3x3 s2 p1 (x), relu of it)."""
+    return _GluePool.apply(x)
+
+
+def glue_relu(a):
+    return _GlueEw.apply(a, None, True)[1]
+
+
+def glue_add_relu(a, s):
+    """(a + s, relu(a + s))."""
+    return _GlueEw.apply(a, s, True)
+
+
+def glue_add(a, s):
+    return _GlueEw.apply(a, s, False)[0]
+
+
+def glue_flatten_relu(x):
+    """relu(x.float()).reshape(N, -1) in logical NCHW order."""
+    return _GlueFlat.apply(x)
+
+
+# ---------------------------------------------------------------------------
 # bf16 MFMA linear layer for the fc behind the trunks (linear_mfma.hip),
 # opt-in with TBAMD_FC_MFMA=1 (--fc_mfma).
 # ---------------------------------------------------------------------------

@@ -35,6 +35,7 @@
 #include "lstm_gate_mfma.h"
 #include "lstm_gate_wide.h"
 #include "lstm_proj_mfma.h"
+#include "resnet_glue.h"
 #include "vtrace_math.h"
 
 namespace tbamd {
@@ -852,6 +853,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("baseline"), py::arg("discounting"), py::arg("clip_reward"),
         py::arg("clip_rho"), py::arg("clip_pg"), py::arg("lambda_"),
         py::arg("baseline_cost"), py::arg("entropy_cost"));
+  m.def("resnet_glue_pool_plan", &tbamd::resnet_glue_pool_plan, py::arg("n"),
+        py::arg("h"), py::arg("w"), py::arg("c"), py::arg("device") = 0);
+  m.def("resnet_glue_pool_fwd", &tbamd::resnet_glue_pool_fwd, py::arg("x"));
+  m.def("resnet_glue_pool_bwd", &tbamd::resnet_glue_pool_bwd, py::arg("g_y"),
+        py::arg("g_r"), py::arg("y"), py::arg("idx"), py::arg("h"),
+        py::arg("w"));
+  m.def("resnet_glue_ew_fwd", &tbamd::resnet_glue_ew_fwd, py::arg("a"),
+        py::arg("s"), py::arg("want_r"));
+  m.def("resnet_glue_ew_bwd", &tbamd::resnet_glue_ew_bwd, py::arg("g_z"),
+        py::arg("g_r"), py::arg("z"));
+  m.def("resnet_glue_flat_fwd", &tbamd::resnet_glue_flat_fwd, py::arg("x"));
+  m.def("resnet_glue_flat_bwd", &tbamd::resnet_glue_flat_bwd, py::arg("g"),
+        py::arg("x"));
   m.def("barrier_probe", &tbamd::barrier_probe);
   m.def("launch_probe", &tbamd::launch_probe);
   m.def("mfma_gemm", &tbamd::mfma_gemm);
